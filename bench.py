@@ -21,10 +21,16 @@ launches, its HBM traffic from the committed rocprofv3 PMC pass (profiles/traffi
 reference SeqAn CPU path (oracle/_ref, compiled from the reference sources) timed on a bounded
 sample on this host's cores.
 
-At N = 1 the same line carries BASELINE.json's other configurations per GPU as sub-records
-(run_other_configs): the production schedule, the host-buffer path, middle scan at 8 kb and 20 kb,
-barcode demux, the configs[1] shape, file-to-file e2e, check_compatibility and approx_counter,
-each with its own oracle spot check and CPU baseline (--sub 0 skips them, --only-subs picks).
+A plain run (--gpus 1 --steps N --warmup W) sets up, warms up, times the N steps and prints the
+result line: the headline figure, ms_per_step and the roofline that the timed steps' own events
+give. --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+
+--full adds everything else: the oracle spot checks, the CPU baselines and, at N = 1, BASELINE.json's
+other configurations per GPU as sub-records of the same line (run_other_configs): the production
+schedule, the host-buffer path, middle scan at 8 kb and 20 kb, barcode demux, the configs[1] shape,
+file-to-file e2e, check_compatibility and approx_counter, each with its own oracle spot check and
+CPU baseline (--sub 0 skips them, --only-subs picks). Without --full, --sub, --only-subs,
+--cpu-sample and the --*check options have no effect.
 """
 import argparse
 import ctypes
@@ -51,6 +57,12 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the oracle spot checks, the CPU '
+                         'baselines and (endtrim) the other configurations as sub-records')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='endtrim / barcodes: after the timed steps, write what the last timed step computed to '
+                         'DIR/<name>.npy (float32; see dump_outputs)')
     ap.add_argument('--reads', type=int, default=100000, help='reads per GPU')
     ap.add_argument('--sets', type=int, default=50)
     ap.add_argument('--end-size', type=int, default=150)
@@ -127,7 +139,13 @@ def parse():
                          '(H2D + kernels + D2H) as sub-records of the same JSON line')
     ap.add_argument('--dist-backend', default='nccl', help='nccl (RCCL over xGMI, default) or gloo (rehearsal of '
                                                            'several ranks sharing one GPU)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ('endtrim', 'barcodes'):
+        ap.error('--dump-outputs is implemented for the endtrim and barcodes workloads')
+    if not args.full:
+        # a plain run: the timed steps and the result line only
+        args.sub = args.cpu_sample = args.check = 0
+    return args
 
 
 def main():
@@ -581,6 +599,12 @@ def run_endtrim(args, rank, world, dist, torch, L, _lib, A, synth, encode_adapte
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda' if args.dist_backend == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        # the last timed step's results: with overlapped steps, the buffer set it wrote
+        last_sres, last_eres = pipe['res'][1 - pipe['set']] if pipe is not None and not timed_fused else (d_sres, d_eres)
+        dump_outputs(args.dump_outputs, rank, L, _lib, n, last_sres, n_sa, last_eres, n_ea, d_st, d_et,
+                     bc['d_call'] if bc is not None else None)
 
     # dominant kernel: average launch duration, start and end launches separately
     dom_ms = [[], []]
@@ -2197,6 +2221,43 @@ def cpu_baseline_middle(reads, trims, mid_adps, sc, thr, threads):
     return {'value': round(len(seqs) / wall, 3), 'unit': 'reads/s', 'cores': threads, 'kind': kind,
             'sample': '%d whole trimmed reads x %d middle adapters (find_middle_adapters loop), %.1f s wall, '
                       'ThreadPool(%d) over ctypes adapterAlignment' % (len(seqs), len(adps), wall, threads)}
+
+
+DUMP_SAMPLE_READS = 4096
+
+
+def dump_outputs(out_dir, rank, L, _lib, n, d_sres, n_sa, d_eres, n_ea, d_st, d_et, d_call):
+    """--dump-outputs: what a caller of the timed step receives, as DIR/<name>.npy in float32 (every
+    value is an int32 far below 2^24, so float32 holds it exactly):
+      start_trim, end_trim              (n,)  the per-read trim decisions (k_end_trim)
+      barcode_call                      (n,)  barcodes workload: the per-read barcode slot
+      sample_reads                      (k,)  the read indices the alignment samples hold: a fixed, seeded
+                                              choice of k = min(n, 4096) reads, ascending
+      start_alignments, end_alignments  (8, adapters, k)  the eight alignment fields (rs, re, as, ae, score,
+                                              m, l1, l2) of every adapter x sampled read, adapters in the
+                                              step's table order
+    The whole alignment tables are 32 B x adapters x n per side (~150 MB each at the headline size),
+    hence the sample; ~15 MB in all at the headline size. Ranks above 0 write <name>.rank<r>.npy."""
+    vp = ctypes.c_void_p
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = '' if rank == 0 else '.rank%d' % rank
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + sfx + '.npy'), np.ascontiguousarray(arr, dtype=np.float32))
+
+    def d2h(d_ptr, shape):
+        a = np.empty(shape, np.int32)
+        _lib.check(L.pcabi_dev_d2h(a.ctypes.data_as(vp), d_ptr, a.nbytes), 'd2h')
+        return a
+
+    pick = np.sort(np.random.default_rng(20240607).choice(n, min(n, DUMP_SAMPLE_READS), replace=False))
+    save('sample_reads', pick)
+    save('start_trim', d2h(d_st, n))
+    save('end_trim', d2h(d_et, n))
+    if d_call is not None:
+        save('barcode_call', d2h(d_call, n))
+    for name, d_res, n_adp in (('start_alignments', d_sres, n_sa), ('end_alignments', d_eres, n_ea)):
+        save(name, d2h(d_res, (8, n_adp, n))[:, :, pick] if n_adp else np.zeros((8, 0, len(pick)), np.int32))
 
 
 def spot_check(L, _lib, d_sres, d_eres, d_st, d_et, s_stride, e_stride, n, n_sa, n_ea, reads, start_adps,

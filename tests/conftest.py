@@ -3,6 +3,10 @@ import subprocess
 import sys
 
 import pytest
+# One HIP runtime per process (custom_porechop_abi_amd/_lib.py): torch's bundled runtime has to be
+# loaded before libpcabi.so. When the whole suite runs in one process, CPU tests load the library
+# before the first GPU test would import torch, and torch then finds no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -43,8 +43,16 @@ def _ranges(positions):
     return out
 
 
+def _share_gpus():
+    """The ranks here compute on the CPU oracle, so the device shards.rank_device() names is never
+    used; on a box with fewer GPUs than ranks (one GPU, a world of 2) it refuses a world without
+    node-local ranks unless sharing is asked for. Without a GPU it counts 0 and takes the rank."""
+    os.environ['PCABI_SHARE_GPUS'] = '1'
+
+
 def _worker(rank, world, port, case_name, out_dir):
     import torch.distributed as dist
+    _share_gpus()
     from custom_porechop_abi_amd import adapters as A, engine, porechop_abi as P, shards
     from custom_porechop_abi_amd.nanopore_read import NanoporeRead
     from tests import oracle_lib
@@ -192,6 +200,7 @@ class _OracleTrimmer(object):
 
 def _file_worker(rank, world, port, case_name, in_path, out_path, res_path, bins=None, chunk=None):
     import torch.distributed as dist
+    _share_gpus()
     from custom_porechop_abi_amd import engine, shards
     from tests import oracle_lib
     engine.align = oracle_lib.align_windows
@@ -337,6 +346,7 @@ ALBACORE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'd
 
 def _albacore_worker(rank, world, port, bins, check, out_path, res_path):
     import torch.distributed as dist
+    _share_gpus()
     from custom_porechop_abi_amd import engine, shards
     from tests import oracle_lib
     engine.align = oracle_lib.align_windows

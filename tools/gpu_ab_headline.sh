@@ -15,7 +15,7 @@ i=0
 IFS=';' read -ra VS <<< "${HEAD_ARGS:---rest-overlap 0;--rest-overlap 1}"
 for v in "${VS[@]}"; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py --sub 0 --cpu-sample 0 $v > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { echo "bench $v failed"; tail -20 $OUT/ab_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --sub 0 --cpu-sample 0 $v > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { echo "bench $v failed"; tail -20 $OUT/ab_$i.err; exit 1; }
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['roofline']['frac'], d['parity_spot_check'])" $OUT/ab_$i.json "$v"
 done
 if [ "${FUZZ:-0}" != "0" ]; then

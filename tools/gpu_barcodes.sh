@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 300 python -u -m pytest -x -v --timeout 120 --timeout-method thread -m gpu ${TESTS:-tests/test_barcode_call.py} > $OUT/pytest_bc.log 2>&1 || { echo "pytest failed rc=$?"; tail -30 $OUT/pytest_bc.log; exit 1; }
 tail -3 $OUT/pytest_bc.log
-timeout -k 10 600 python bench.py --workload barcodes ${BENCH_ARGS:-} > $OUT/bench_barcodes.json 2> $OUT/bench_barcodes.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_barcodes.err; exit 1; }
+timeout -k 10 600 python bench.py --full --workload barcodes ${BENCH_ARGS:-} > $OUT/bench_barcodes.json 2> $OUT/bench_barcodes.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_barcodes.err; exit 1; }
 cat $OUT/bench_barcodes.json
 export TMPDIR=/tmp
 cd /tmp

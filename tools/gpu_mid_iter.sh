@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 500 python -u -m pytest -x -v --timeout 120 --timeout-method thread -m gpu ${TESTS:-tests/test_gpu_parity.py tests/test_gpu_long.py tests/test_gpu_freegap.py tests/test_pipeline.py} > $OUT/pytest_mid.log 2>&1 || { echo "pytest failed rc=$?"; tail -40 $OUT/pytest_mid.log; exit 1; }
 tail -2 $OUT/pytest_mid.log
-timeout -k 10 300 python bench.py --only-subs middle,middle_20kb --steps 10 ${ARGS:-} > $OUT/bench_mid.json 2> $OUT/bench_mid.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_mid.err; exit 1; }
+timeout -k 10 300 python bench.py --full --only-subs middle,middle_20kb --steps 10 ${ARGS:-} > $OUT/bench_mid.json 2> $OUT/bench_mid.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_mid.err; exit 1; }
 python - $OUT/bench_mid.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd $R
-timeout -k 10 900 python bench.py --workload middle --reads ${MID_READS:-100000} --steps ${MID_STEPS:-3} --warmup 1 > $OUT/bench_middle.json 2> $OUT/bench_middle.err || { echo "middle bench failed"; tail -5 $OUT/bench_middle.err; exit 1; }
+timeout -k 10 900 python bench.py --full --workload middle --reads ${MID_READS:-100000} --steps ${MID_STEPS:-3} --warmup 1 > $OUT/bench_middle.json 2> $OUT/bench_middle.err || { echo "middle bench failed"; tail -5 $OUT/bench_middle.err; exit 1; }
 cat $OUT/bench_middle.json
 export TMPDIR=/tmp
 cd /tmp

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method thread -m gpu ${TESTS:-tests} > $OUT/pytest_gpu.log 2>&1 || { echo "pytest failed rc=$?"; tail -40 $OUT/pytest_gpu.log; exit 1; }
 tail -2 $OUT/pytest_gpu.log
-timeout -k 10 300 python bench.py --sub 0 ${BENCH_ARGS:-} > $OUT/bench_q.json 2> $OUT/bench_q.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_q.err; exit 1; }
+timeout -k 10 300 python bench.py --full --sub 0 ${BENCH_ARGS:-} > $OUT/bench_q.json 2> $OUT/bench_q.err || { echo "bench failed rc=$?"; tail -20 $OUT/bench_q.err; exit 1; }
 cat $OUT/bench_q.json | cut -c1-600
 export TMPDIR=/tmp
 cd /tmp

@@ -8,7 +8,7 @@ cd $R
 mkdir -p gpurun_out
 for n in ${RANKS:-2 4}; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-      --master-port $((29500 + n)) bench.py --gpus $n --steps 10 --warmup 2 --dist-backend gloo ${BENCH_ARGS:-} \
+      --master-port $((29500 + n)) bench.py --full --gpus $n --steps 10 --warmup 2 --dist-backend gloo ${BENCH_ARGS:-} \
       > gpurun_out/rehearse_n$n.json 2> gpurun_out/rehearse_n$n.err || { echo "n=$n failed"; tail -5 gpurun_out/rehearse_n$n.err; exit 1; }
   echo "n=$n: $(tail -1 gpurun_out/rehearse_n$n.json)"
 done
