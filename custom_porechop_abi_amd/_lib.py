@@ -114,6 +114,16 @@ def lib():
                                       c_p, c_p, c_i64, c_p, c_p, ctypes.c_int32, c_p, ctypes.c_int32, c_p], c_int),
         'pcabi_flag_list_dev': ([c_p, ctypes.c_int32, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p], c_int),
         'pcabi_trim_views_dev': ([c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p], c_int),
+        'pcabi_max_path_adapter_len': ([], c_int),
+        'pcabi_paths_scratch_pairs': ([], c_i64),
+        'pcabi_align_paths_host': ([c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_i64,
+                                    c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_i64], c_i64),
+        'pcabi_align_paths_dev': ([c_p, c_p, c_p, c_i64, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_i64, c_int, c_int,
+                                   c_int, c_int, c_p, c_p, c_p, c_i64, c_p], c_i64),
+        'pcabi_adapter_profile_dev': ([c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, ctypes.c_int32,
+                                       ctypes.c_int32, c_p, c_p], c_int),
+        'pcabi_adapter_profile_host': ([c_int, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64,
+                                        ctypes.c_int32, ctypes.c_int32, c_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -145,7 +155,9 @@ def exported_symbols():
             'pcabi_compat_all_vs_all_host', 'pcabi_kmer_count_host', 'pcabi_kmer_top_host', 'pcabi_gather_host',
             'pcabi_kmer_approx_host', 'pcabi_io_release_cache', 'pcabi_best_full_identity_host',
             'pcabi_middle_cuts_dev', 'pcabi_middle_cuts_host', 'pcabi_fastx_record_start', 'pcabi_fastx_set_range', 'pcabi_fastx_next_text',
-            'pcabi_end_decisions_host', 'pcabi_end_decisions_seqs', 'pcabi_stage_seqs_host', 'pcabi_flag_list_dev', 'pcabi_trim_views_dev']
+            'pcabi_end_decisions_host', 'pcabi_end_decisions_seqs', 'pcabi_stage_seqs_host', 'pcabi_flag_list_dev', 'pcabi_trim_views_dev',
+            'pcabi_max_path_adapter_len', 'pcabi_paths_scratch_pairs', 'pcabi_align_paths_host', 'pcabi_align_paths_dev',
+            'pcabi_adapter_profile_dev', 'pcabi_adapter_profile_host']
 
 
 class CrossRegion(ctypes.Structure):

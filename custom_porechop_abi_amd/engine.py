@@ -500,3 +500,131 @@ def barcode_call(start_res, end_res, start_slots, end_slots, n_read, barcode_thr
                                            _ptr(scores) if with_scores else None)
         check(rc, 'pcabi_barcode_call_host')
     return (call, scores) if with_scores else call
+
+
+# ---- alignment paths and adapter profiles (include/pcabi.h, csrc/pcabi_paths.hip) ------------------
+OP_MATCH, OP_MISMATCH, OP_READ_ONLY, OP_ADAPTER_ONLY = range(4)
+PROFILE_COLS = ('A', 'C', 'G', 'T', 'N', 'DEL', 'INS')
+_DNA5_LETTERS = 'ACGTN'
+_PATH_RUNS_RATIO = [8.0]
+
+
+def _path_inputs(windows, adapter_seqs, pairs):
+    codes, offs, lens = windows
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    tw = np.ascontiguousarray(pairs[0], dtype=np.int32)
+    ta = np.ascontiguousarray(pairs[1], dtype=np.int32)
+    if len(tw) != len(ta):
+        raise ValueError('pairs: the two index arrays differ in length')
+    return codes, offs, lens, encode_adapters(adapter_seqs), tw, ta
+
+
+def align_paths(windows, adapter_seqs, scoring_scheme_vals, pairs, device=0):
+    """The alignments themselves for explicit (window, adapter) pairs (pcabi_align_paths_host).
+
+    windows / pairs as for align. Returns (res, run_off, runs): res int32 (8, n) the fields align
+    returns for the pairs; runs uint32, the columns of the gapped rows left to right, run-length
+    encoded as (run_length << 2) | op (OP_MATCH, OP_MISMATCH, OP_READ_ONLY, OP_ADAPTER_ONLY); the
+    runs of pair t are runs[run_off[t]:run_off[t + 1]] (none for an empty window). The run buffer
+    grows and the call runs again when it was too small, as middle_scan does for its hits."""
+    codes, offs, lens, (acodes, aoffs, alens), tw, ta = _path_inputs(windows, adapter_seqs, pairs)
+    n = len(tw)
+    res = np.zeros((NFIELDS, n), dtype=np.int32)
+    run_off = np.zeros(n + 1, dtype=np.int64)
+    if n == 0:
+        return res, run_off, np.zeros(0, np.uint32)
+    m, mm, go, ge = (int(x) for x in scoring_scheme_vals[:4])
+    cap = int(n * _PATH_RUNS_RATIO[0] * 1.25) + 1024
+    while True:
+        runs = np.empty(cap, dtype=np.uint32)
+        total = lib().pcabi_align_paths_host(device, _ptr(codes), codes.size, _ptr(offs), _ptr(lens), len(lens),
+                                             _ptr(acodes), _ptr(aoffs), _ptr(alens), len(alens), _ptr(tw), _ptr(ta), n,
+                                             m, mm, go, ge, _ptr(res), _ptr(run_off), _ptr(runs), cap)
+        if total < 0:
+            check(int(total), 'pcabi_align_paths_host')
+        _PATH_RUNS_RATIO[0] = max(_PATH_RUNS_RATIO[0], float(total) / n)
+        if total <= cap:
+            return res, run_off, runs[:total]
+        cap = int(total)
+
+
+def path_ops(runs):
+    """One op per column (uint8) from a pair's run list."""
+    runs = np.asarray(runs, dtype=np.uint32)
+    return np.repeat((runs & 3).astype(np.uint8), (runs >> 2).astype(np.int64))
+
+
+def path_rows(runs, read, adapter):
+    """(read_row, adapter_row): the gapped rows of a pair's run list as text, '-' for gaps and ACGTN
+    letters (the way SeqAn prints Dna5: anything that is not A, C, G, T or U shows as N). No runs
+    (no alignment: an empty sequence) give two empty rows."""
+    ops = path_ops(runs)
+    if len(ops) == 0:
+        return '', ''
+    rc, ac = encode_seq(read), encode_seq(adapter)
+    has_r, has_a = ops != OP_ADAPTER_ONLY, ops != OP_READ_ONLY
+    if int(has_r.sum()) != len(rc) or int(has_a.sum()) != len(ac):
+        raise ValueError('path_rows: the run list does not belong to these sequences')
+    letters = np.frombuffer((_DNA5_LETTERS + '-').encode(), np.uint8)
+    rr = np.full(len(ops), 5, np.uint8)
+    ar = np.full(len(ops), 5, np.uint8)
+    rr[has_r] = rc
+    ar[has_a] = ac
+    return letters[rr].tobytes().decode(), letters[ar].tobytes().decode()
+
+
+def path_fields(runs):
+    """ScoredAlignment's rules (porechop_abi/src/alignment.cpp:6-110) over a pair's run list, on the
+    CPU: [rs, re, as, ae, m, l1, l2] -- align's fields without the score; rs = -1 for no runs."""
+    ops = path_ops(runs)
+    if len(ops) == 0:
+        return [-1, -1, -1, -1, 0, 0, 0]
+    has_r, has_a = ops != OP_ADAPTER_ONLY, ops != OP_READ_ONLY
+    rb = np.concatenate([[0], np.cumsum(has_r)])        # bases before each column
+    ab = np.concatenate([[0], np.cumsum(has_a)])
+    # the first column with a base seen in both rows, and the same from the right
+    st = int(max(np.argmax(has_r), np.argmax(has_a)))
+    n = len(ops)
+    en = int(n - 1 - max(np.argmax(has_r[::-1]), np.argmax(has_a[::-1])))
+    a_pos = np.flatnonzero(has_a)
+    a0, a1 = int(a_pos[0]), int(a_pos[-1])
+    m = int((ops[st:en + 1] == OP_MATCH).sum())
+    return [int(rb[st]), int(rb[en]), int(ab[st]), int(ab[en]), m, en - st + 1, a1 - a0 + 1]
+
+
+def format_alignment(runs, read, adapter):
+    """Three lines of text: the read row, '|' under the matching columns, the adapter row."""
+    rr, ar = path_rows(runs, read, adapter)
+    mid = ''.join('|' if op == OP_MATCH else ' ' for op in path_ops(runs).tolist())
+    return '%s\n%s\n%s' % (rr, mid, ar)
+
+
+def adapter_profile(windows, adapter_seqs, scoring_scheme_vals, pairs, select=None, counts=None, device=0):
+    """Per-position pileup of the windows over their adapters on the GPU (pcabi_align_paths_host,
+    then pcabi_adapter_profile_host): int64 (n_adp, longest adapter, 7) counts of A, C, G, T, N,
+    DEL, INS (PROFILE_COLS) per adapter position, over the aligned region of every pair (select: a
+    boolean per pair, None = all). counts: an earlier result to add to (returned updated)."""
+    codes, offs, lens, (acodes, aoffs, alens), tw, ta = _path_inputs(windows, adapter_seqs, pairs)
+    n_adp = len(alens)
+    max_len = int(alens.max()) if n_adp else 0
+    if counts is None:
+        counts = np.zeros((n_adp, max_len, len(PROFILE_COLS)), np.int64)
+    else:
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if counts.shape != (n_adp, max_len, len(PROFILE_COLS)):
+            raise ValueError('adapter_profile: counts has shape %r, not %r'
+                             % (counts.shape, (n_adp, max_len, len(PROFILE_COLS))))
+    if len(tw) == 0 or counts.size == 0:
+        return counts
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.uint8)
+    if sel is not None and len(sel) != len(tw):
+        raise ValueError('adapter_profile: select has %d entries for %d pairs' % (len(sel), len(tw)))
+    res, run_off, runs = align_paths((codes, offs, lens), adapter_seqs, scoring_scheme_vals, (tw, ta), device)
+    rs = np.ascontiguousarray(res[0])
+    rc = lib().pcabi_adapter_profile_host(device, _ptr(rs), _ptr(run_off), _ptr(runs), _ptr(codes), codes.size,
+                                          _ptr(offs), _ptr(lens), len(lens), _ptr(tw), _ptr(ta), _ptr(sel), len(tw),
+                                          n_adp, max_len, _ptr(counts))
+    check(rc, 'pcabi_adapter_profile_host')
+    return counts

@@ -114,6 +114,72 @@ int pcabi_align_host(int device,
                      int match, int mismatch, int gap_open, int gap_extend,
                      int32_t *out);
 
+/* ---- alignment paths and adapter profiles (csrc/pcabi_paths.hip) ------------------------ */
+/*
+ * The alignment itself, for explicit (window, adapter) pairs: the columns of the gapped rows SeqAn's
+ * globalAlignment(..., AlignConfig<1,1,1,1>) leaves in Align (head free-gap columns, the traceback
+ * path, tail free-gap columns), left to right, one op per column:
+ *   MATCH        both rows hold the same Dna5 code (N against N is a match)
+ *   MISMATCH     both rows hold a base, the codes differ
+ *   READ_ONLY    a read base against a gap in the adapter row
+ *   ADAPTER_ONLY an adapter base against a gap in the read row
+ * run-length encoded as uint32 = (run_length << 2) | op, neighbouring runs of different ops. The
+ * runs of pair t are runs[run_off[t] .. run_off[t + 1]) (run_off has n_task + 1 entries); a pair with
+ * an empty window has none. For any other pair ops 0 + 1 + 2 add up to the window length and ops
+ * 0 + 1 + 3 to the adapter length. out (int32[PCABI_NFIELDS * n_task], row f = field f) receives the
+ * same eight fields pcabi_align_host returns for the pairs, computed from these columns.
+ * Inputs are laid out as for pcabi_align_host (task_win / task_adp are required) and never written.
+ * Adapters of 1..pcabi_max_path_adapter_len() = 128 bases, any four-integer scoring. A pair's trace
+ * lives in LDS when it fits a wavefront's share and in device scratch otherwise; the pairs run in
+ * rounds whose scratch stays within PCABI_PATHS_SCRATCH_MB (default 256), and a pair whose trace
+ * alone, (window + adapter / 2) x adapter bytes, exceeds it is refused with PCABI_E_ARG.
+ * Both return the total number of runs or a negative PCABI_E_*. When the total exceeds runs_cap, out
+ * and run_off are complete and runs is undefined: call again with a larger buffer (the convention of
+ * pcabi_middle_scan_dev). Bad arguments are refused before anything is launched.
+ *   pcabi_align_paths_host : host buffers.
+ *   pcabi_align_paths_dev  : every pointer a device pointer on the current device, queued on
+ *                            `stream`, which the call synchronises (twice: it reads the lengths
+ *                            and the pairs to plan the rounds, and the total at the end).
+ *   pcabi_paths_scratch_pairs : pairs whose trace went to device scratch so far, process-wide.
+ */
+enum { PCABI_OP_MATCH = 0, PCABI_OP_MISMATCH = 1, PCABI_OP_READ_ONLY = 2, PCABI_OP_ADAPTER_ONLY = 3 };
+int pcabi_max_path_adapter_len(void);
+int64_t pcabi_paths_scratch_pairs(void);
+int64_t pcabi_align_paths_host(int device, const uint8_t *codes, int64_t codes_len, const int64_t *win_off,
+                               const int32_t *win_len, int64_t n_win, const uint8_t *adp_codes,
+                               const int32_t *adp_off, const int32_t *adp_len, int32_t n_adp,
+                               const int32_t *task_win, const int32_t *task_adp, int64_t n_task, int match,
+                               int mismatch, int gap_open, int gap_extend, int32_t *out, int64_t *run_off,
+                               uint32_t *runs, int64_t runs_cap);
+int64_t pcabi_align_paths_dev(const uint8_t *codes, const int64_t *win_off, const int32_t *win_len, int64_t n_win,
+                              const uint8_t *adp_codes, const int32_t *adp_off, const int32_t *adp_len,
+                              int32_t n_adp, const int32_t *task_win, const int32_t *task_adp, int64_t n_task,
+                              int match, int mismatch, int gap_open, int gap_extend, int32_t *out,
+                              int64_t *run_off, uint32_t *runs, int64_t runs_cap, void *stream);
+/*
+ * Per-position pileup of the reads over their adapters, from the run lists above: counts
+ * (int64[n_adp * max_adp_len * PCABI_PROFILE_NCOL], row-major) is ADDED to, so batches accumulate.
+ * Only the columns of the aligned region count (the region l1 is measured over, alignment.cpp:28-52;
+ * free end-gap columns never do). For adapter position i: the read base aligned to it (MATCH and
+ * MISMATCH alike) counts under A..N, an ADAPTER_ONLY column under DEL, and every READ_ONLY base
+ * under INS at the position of the last adapter base to its left (position 0 if there is none).
+ * select (uint8[n_task], NULL = every pair) picks the pairs; res (the rs row of the pairs' results,
+ * or NULL) skips pairs without an alignment. Positions >= max_adp_len are dropped.
+ *   pcabi_adapter_profile_dev  : device pointers, asynchronous on `stream`.
+ *   pcabi_adapter_profile_host : host buffers (windows as for pcabi_align_host).
+ */
+enum { PCABI_PROFILE_A = 0, PCABI_PROFILE_C = 1, PCABI_PROFILE_G = 2, PCABI_PROFILE_T = 3, PCABI_PROFILE_N = 4,
+       PCABI_PROFILE_DEL = 5, PCABI_PROFILE_INS = 6, PCABI_PROFILE_NCOL = 7 };
+int pcabi_adapter_profile_dev(const int32_t *res, const int64_t *run_off, const uint32_t *runs,
+                              const uint8_t *codes, const int64_t *win_off, const int32_t *win_len,
+                              const int32_t *task_win, const int32_t *task_adp, const uint8_t *select,
+                              int64_t n_task, int32_t n_adp, int32_t max_adp_len, int64_t *counts, void *stream);
+int pcabi_adapter_profile_host(int device, const int32_t *res, const int64_t *run_off, const uint32_t *runs,
+                               const uint8_t *codes, int64_t codes_len, const int64_t *win_off,
+                               const int32_t *win_len, int64_t n_win, const int32_t *task_win,
+                               const int32_t *task_adp, const uint8_t *select, int64_t n_task, int32_t n_adp,
+                               int32_t max_adp_len, int64_t *counts);
+
 /* ---- device-resident interface (bench / multi-GPU shards) ------------------------------ */
 /* Thin HIP wrappers so hosts without a GPU framework can keep inputs resident in HBM. */
 int pcabi_dev_set(int device);
