@@ -124,6 +124,15 @@ def lib():
                                        ctypes.c_int32, c_p, c_p], c_int),
         'pcabi_adapter_profile_host': ([c_int, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64,
                                         ctypes.c_int32, ctypes.c_int32, c_p], c_int),
+        'pcabi_gzip_block_len': ([], c_int),
+        'pcabi_gzip_bound': ([c_i64, c_i64], c_i64),
+        'pcabi_gzip_scratch_bytes': ([c_i64, c_i64], c_i64),
+        'pcabi_gzip_tune': ([c_int, c_i64, c_i64], c_int),
+        'pcabi_gzip_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64], c_int),
+        'pcabi_gzip_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_i64),
+        'pcabi_gzip_plan_lines': ([c_p, c_i64, c_i64, c_i64, c_p, c_i64], c_i64),
+        'pcabi_gzip_last_times': ([c_p, c_p, c_p], None),
+        'pcabi_reads_write_last_times': ([c_p, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -157,7 +166,10 @@ def exported_symbols():
             'pcabi_middle_cuts_dev', 'pcabi_middle_cuts_host', 'pcabi_fastx_record_start', 'pcabi_fastx_set_range', 'pcabi_fastx_next_text',
             'pcabi_end_decisions_host', 'pcabi_end_decisions_seqs', 'pcabi_stage_seqs_host', 'pcabi_flag_list_dev', 'pcabi_trim_views_dev',
             'pcabi_max_path_adapter_len', 'pcabi_paths_scratch_pairs', 'pcabi_align_paths_host', 'pcabi_align_paths_dev',
-            'pcabi_adapter_profile_dev', 'pcabi_adapter_profile_host']
+            'pcabi_adapter_profile_dev', 'pcabi_adapter_profile_host', 'pcabi_reads_write_dev',
+            'pcabi_gzip_block_len', 'pcabi_gzip_bound', 'pcabi_gzip_scratch_bytes', 'pcabi_gzip_tune', 'pcabi_gzip_dev',
+            'pcabi_gzip_host', 'pcabi_gzip_plan_lines', 'pcabi_gzip_last_times',
+            'pcabi_reads_write_last_times']
 
 
 class CrossRegion(ctypes.Structure):

@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "../../include/pcabi.h"
+#include "pcabi_deflate.h"
 
 namespace pcabi_internal {
 int fail(int code, const std::string &msg);   // pcabi_engine.hip: pcabi_last_error()
@@ -1100,13 +1101,21 @@ void put_record(S &o, bool fasta, const char *name, size_t nn, bool own, const c
 
 }  // namespace
 
-extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
-                                 const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
-                                 const int64_t *cuts, int min_split_read_size, int discard_middle,
-                                 int untrimmed, const uint8_t *select) {
+// seconds the calling thread's last pcabi_reads_write* spent laying the records out (sizing, fill,
+// block planning), compressing (gz = 2: pcabi_gzip_host) and writing the file
+static thread_local double g_write_times[3] = {0, 0, 0};
+static double wall_s() {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+static int reads_write_impl(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                            const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                            const int64_t *cuts, int min_split_read_size, int discard_middle,
+                            int untrimmed, const uint8_t *select, int gzip_device) {
     if (!b || !path) return fail(PCABI_E_ARG, "bad arguments");
+    if (gz == 2 && std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "gz = 2 writes files, not stdout");
     Sink o;
-    if (gz) {
+    if (gz != 0 && gz != 2) {   // any other non-zero value keeps meaning zlib
         o.gz = gzopen(path, append ? "ab" : "wb");
         if (!o.gz) return fail(PCABI_E_ARG, std::string("could not write ") + path);
     } else if (std::strcmp(path, "-") == 0) {
@@ -1184,7 +1193,25 @@ extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int app
     // calls -- a writev of ~7 small pieces per record spent more on the pieces than on the bytes
     // (e2e writer 8.1 GB/s against 11.9 for one contiguous buffer, bench write_probe).
     int64_t emitted = 0;
+    g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
+    const double t_begin = wall_s();
     const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
+    // gz = 2: the same buffer, cut into blocks at line ends by the thread that filled each range
+    // (pcabi_deflate.h plan_blocks), compressed on the device and written as gzip members.
+    std::vector<char, NoInit<char>> out;
+    std::vector<std::vector<int64_t>> ends((size_t)std::max(nt, 1));
+    auto write_all = [&](const char *p, size_t n) {
+        size_t k = 0;
+        while (o.ok && k < n) {
+            const ssize_t w = ::write(o.fd, p + k, std::min<size_t>(n - k, 256u << 20));
+            if (w < 0) {
+                if (errno == EINTR) continue;
+                o.ok = false;
+                break;
+            }
+            k += (size_t)w;
+        }
+    };
     if (o.fd >= 0 && b->n > 0) {
         std::vector<int64_t> lo((size_t)nt + 1), bytes((size_t)nt + 1, 0), emit((size_t)nt, 0);
         for (int t = 0; t <= nt; ++t) lo[(size_t)t] = b->n * t / nt;
@@ -1204,7 +1231,6 @@ extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int app
             bytes[(size_t)t + 1] = (int64_t)c.n;
         });
         for (int t = 0; t < nt; ++t) bytes[(size_t)t + 1] += bytes[(size_t)t];
-        std::vector<char, NoInit<char>> out;
         out.resize((size_t)bytes[(size_t)nt]);
         par([&](int t) {
             std::vector<std::pair<int64_t, int64_t>> rg;
@@ -1212,21 +1238,38 @@ extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int app
             int64_t e = 0;
             for (int64_t i = lo[(size_t)t]; i < lo[(size_t)t + 1]; ++i) e += format(i, m, rg) ? 1 : 0;
             emit[(size_t)t] = e;
+            if (gz == 2)
+                pcabi_deflate::plan_blocks(out.data(), bytes[(size_t)t], bytes[(size_t)t + 1], PCABI_GZIP_LONG_LINE,
+                                           PCABI_GZIP_BLOCK_CAP, [&](int64_t end) { ends[(size_t)t].push_back(end); });
         });
         for (int t = 0; t < nt; ++t) emitted += emit[(size_t)t];
-        size_t k = 0;
-        while (o.ok && k < out.size()) {
-            const ssize_t w = ::write(o.fd, out.data() + k, std::min<size_t>(out.size() - k, 256u << 20));
-            if (w < 0) {
-                if (errno == EINTR) continue;
-                o.ok = false;
-                break;
-            }
-            k += (size_t)w;
+        g_write_times[0] = wall_s() - t_begin;
+        if (gz != 2) {
+            const double t0 = wall_s();
+            write_all(out.data(), out.size());
+            g_write_times[2] = wall_s() - t0;
         }
     } else {
         std::vector<std::pair<int64_t, int64_t>> rg;
         for (int64_t i = 0; i < b->n; ++i) emitted += format(i, o, rg) ? 1 : 0;
+    }
+    if (gz == 2) {
+        std::vector<int64_t> block_off{0};
+        for (const auto &v : ends) block_off.insert(block_off.end(), v.begin(), v.end());
+        const int64_t nblk = (int64_t)block_off.size() - 1;
+        std::vector<uint8_t, NoInit<uint8_t>> z;
+        z.resize((size_t)pcabi_gzip_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1)));
+        const double t0 = wall_s();
+        const int64_t zn = pcabi_gzip_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
+                                           block_off.data(), nblk, z.data(), (int64_t)z.size());
+        g_write_times[1] = wall_s() - t0;
+        if (zn < 0 || zn > (int64_t)z.size()) {
+            ::close(o.fd);
+            return zn < 0 ? (int)zn : fail(PCABI_E_ARG, "gzip capacity bound exceeded");
+        }
+        const double t1 = wall_s();
+        write_all((const char *)z.data(), (size_t)zn);
+        g_write_times[2] = wall_s() - t1;
     }
     o.flush();
     const bool ok = o.ok;
@@ -1235,4 +1278,39 @@ extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int app
     else if (o.fp) std::fflush(o.fp);
     if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
     return (int)std::min<int64_t>(emitted, INT32_MAX);
+}
+
+extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                                 const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                                 const int64_t *cuts, int min_split_read_size, int discard_middle,
+                                 int untrimmed, const uint8_t *select) {
+    return reads_write_impl(b, path, append, gz, fasta, start_trim, end_trim, cut_off, cuts, min_split_read_size,
+                            discard_middle, untrimmed, select, -1);
+}
+
+extern "C" int pcabi_reads_write_dev(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                                     const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                                     const int64_t *cuts, int min_split_read_size, int discard_middle,
+                                     int untrimmed, const uint8_t *select, int gzip_device) {
+    return reads_write_impl(b, path, append, gz, fasta, start_trim, end_trim, cut_off, cuts, min_split_read_size,
+                            discard_middle, untrimmed, select, gzip_device);
+}
+
+extern "C" void pcabi_reads_write_last_times(double *layout, double *compress, double *write) {
+    if (layout) *layout = g_write_times[0];
+    if (compress) *compress = g_write_times[1];
+    if (write) *write = g_write_times[2];
+}
+
+extern "C" int64_t pcabi_gzip_plan_lines(const char *text, int64_t n, int64_t long_line, int64_t cap,
+                                         int64_t *block_off, int64_t off_cap) {
+    if (n < 0 || (n > 0 && !text) || long_line < 1 || cap < long_line || cap > PCABI_GZIP_BLOCK_CAP)
+        return fail(PCABI_E_ARG, "1 <= long_line <= cap <= 65535");
+    int64_t k = 0;
+    if (block_off && off_cap > 0) block_off[0] = 0;
+    pcabi_deflate::plan_blocks(text, 0, n, long_line, cap, [&](int64_t end) {
+        ++k;
+        if (block_off && k < off_cap) block_off[k] = end;
+    });
+    return k;
 }

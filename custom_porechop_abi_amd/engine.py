@@ -628,3 +628,58 @@ def adapter_profile(windows, adapter_seqs, scoring_scheme_vals, pairs, select=No
                                           n_adp, max_len, _ptr(counts))
     check(rc, 'pcabi_adapter_profile_host')
     return counts
+
+
+# ---- gzip on the device (csrc/pcabi_deflate.hip) -------------------------------------------------
+GZIP_LONG_LINE = 1024     # include/pcabi.h PCABI_GZIP_LONG_LINE
+GZIP_BLOCK_CAP = 65535    # include/pcabi.h PCABI_GZIP_BLOCK_CAP
+
+
+def _gzip_input(data, blocks):
+    buf = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(data, np.uint8).reshape(-1)
+    off = None if blocks is None else np.ascontiguousarray(blocks, np.int64)
+    if off is not None and (off.ndim != 1 or off.size < 1):
+        raise ValueError('blocks is the CSR list block_off[n_blocks + 1]')
+    return buf, off
+
+
+def gzip_block_len():
+    """The fixed block length used when no block list is given (pcabi_gzip_block_len)."""
+    return int(lib().pcabi_gzip_block_len())
+
+
+def gzip_bound(n, n_blocks=0):
+    """Capacity that always holds the stream of n bytes in n_blocks blocks (0: fixed blocks)."""
+    return int(lib().pcabi_gzip_bound(int(n), int(n_blocks)))
+
+
+def gzip_line_blocks(data, long_line=GZIP_LONG_LINE, cap=GZIP_BLOCK_CAP):
+    """The writer's line-aligned block list for text (pcabi_gzip_plan_lines): int64 block_off."""
+    buf, _ = _gzip_input(data, None)
+    L = lib()
+    nb = L.pcabi_gzip_plan_lines(_ptr(buf), buf.size, int(long_line), int(cap), None, 0)
+    if nb < 0:
+        check(int(nb), 'pcabi_gzip_plan_lines')
+    off = np.zeros(nb + 1, np.int64)
+    L.pcabi_gzip_plan_lines(_ptr(buf), buf.size, int(long_line), int(cap), _ptr(off), off.size)
+    return off
+
+
+def gzip_compress(data, blocks=None, device=0, cap=None):
+    """data (bytes or a uint8 array) as a gzip stream compressed on GPU `device` (pcabi_gzip_host):
+    Huffman-only deflate, one block per entry of blocks (block_off[n_blocks + 1], every block 1..65535
+    bytes; None: fixed blocks of gzip_block_len()), possibly several gzip members. Returns bytes.
+    cap (tests): the output capacity offered; a too small one raises ValueError naming the size
+    needed."""
+    buf, off = _gzip_input(data, blocks)
+    L = lib()
+    nb = 0 if off is None else off.size - 1
+    size = gzip_bound(buf.size, nb) if cap is None else int(cap)
+    out = np.empty(max(size, 1), np.uint8)
+    n = L.pcabi_gzip_host(int(device), _ptr(buf), buf.size, None if off is None else _ptr(off), nb, _ptr(out), size)
+    if n < 0:
+        check(int(n), 'pcabi_gzip_host')
+    if n > size:
+        raise ValueError('gzip_compress: capacity %d, needed %d' % (size, n))
+    return out[:n].tobytes()

@@ -47,6 +47,8 @@ def _declare(L):
         'pcabi_reads_views': ([P, ctypes.POINTER(_View)], c_int),
         'pcabi_reads_free': ([P], None),
         'pcabi_reads_write': ([P, ctypes.c_char_p, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P], c_int),
+        'pcabi_reads_write_dev': ([P, ctypes.c_char_p, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P, c_int],
+                                  c_int),
         'pcabi_fastx_record_start': ([P, i64], i64),
         'pcabi_fastx_set_range': ([P, i64, i64], c_int),
         'pcabi_fastx_remaining': ([P], i64),
@@ -416,9 +418,11 @@ def get_albacore_barcode_from_path(albacore_path):
 
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
-                cut_arrays=None):
+                cut_arrays=None, gzip_device=None):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
+    gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
+    that GPU (pcabi_reads_write_dev, gz = 2: a multi-member gzip file of the same text).
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -445,8 +449,13 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
         cu = np.array(flat if flat else [0, 0], np.int64)
     sel = None if select is None else np.ascontiguousarray(select, np.uint8)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-    rc = L.pcabi_reads_write(batch._h, os.fsencode(path), int(append), int(gz), int(fasta), p(st), p(et), p(co), p(cu),
-                             int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel))
+    if gz and gzip_device is not None:
+        rc = L.pcabi_reads_write_dev(batch._h, os.fsencode(path), int(append), 2, int(fasta), p(st), p(et), p(co),
+                                     p(cu), int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel),
+                                     int(gzip_device))
+    else:
+        rc = L.pcabi_reads_write(batch._h, os.fsencode(path), int(append), int(gz), int(fasta), p(st), p(et), p(co),
+                                 p(cu), int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel))
     if rc < 0:
         check(rc, 'pcabi_reads_write')
     return int(rc)

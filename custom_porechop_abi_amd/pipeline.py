@@ -38,15 +38,18 @@ class FileTrimmer(object):
     False, adapter filter on (the fork's)."""
 
     barcode_dir = None                    # -b off (set by __init__)
+    gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
                  extra_middle_trim_bad_side=100, min_split_read_size=1000, no_split=False, discard_middle=False,
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
-                 discard_unassigned=False):
+                 discard_unassigned=False, gzip_on_device=False):
         self.L = L = lib()
         self.device = int(device)
+        # '.gz' output formats: zlib on the host (default) or the device encoder (misc.write_reads)
+        self.gzip_device = self.device if gzip_on_device else None
         check(L.pcabi_dev_set(device), 'pcabi_dev_set')
         self.sc = tuple(int(x) for x in scoring_scheme_vals[:4])
         self.E, self.thr, self.extra, self.min_trim = int(end_size), float(end_threshold), int(extra_end_trim), \
@@ -319,7 +322,8 @@ class FileTrimmer(object):
                     else:
                         at = os.path.getsize(out_path) if (segments is not None and not first) else 0
                         misc.write_reads(b, out_path, out_format, st, et, None, self.min_split, self.discard_middle,
-                                         select=keep, append=not first, cut_arrays=(co, cu))
+                                         select=keep, append=not first, cut_arrays=(co, cu),
+                                         gzip_device=getattr(self, 'gzip_device', None))
                         if segments is not None:
                             segments.append((k, at, os.path.getsize(out_path)))
                 except BaseException as ex:
@@ -388,7 +392,8 @@ class FileTrimmer(object):
             fresh = name not in bins
             at = 0 if fresh else os.path.getsize(path)
             emitted = misc.write_reads(b, path, out_format, st, et, None, self.min_split, self.discard_middle,
-                                       untrimmed=self.untrimmed, select=mask, append=not fresh, cut_arrays=(co, cu))
+                                       untrimmed=self.untrimmed, select=mask, append=not fresh, cut_arrays=(co, cu),
+                                       gzip_device=getattr(self, 'gzip_device', None))
             if emitted == 0:
                 if fresh and os.path.exists(path):
                     os.remove(path)             # the reference never opens an empty bin

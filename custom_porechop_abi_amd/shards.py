@@ -370,7 +370,7 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
                       check_reads=10000, adapter_threshold=90.0, max_reads=100000, group=None, device=None,
                       trimmer_factory=None, barcode_dir=None, barcode_threshold=75.0, barcode_diff=5.0,
                       require_two_barcodes=False, untrimmed=False, discard_unassigned=False, inflate_dir=None,
-                      spool_chunk_bytes=None):
+                      spool_chunk_bytes=None, gzip_on_device=False):
     """The CLI's file-to-file path (porechop_abi.py:41-131: adapter-set search on the first
     check_reads records, end trim, middle scan, the fork's filter, trimmed output) on every rank of
     `group`, one GPU each:
@@ -392,6 +392,9 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
     With barcode_dir (-b) every rank writes its bins into a private directory, recording the
     byte span of each bin write, and rank 0 stitches every bin in record order; the barcoding
     kit direction comes from choose_barcoding_kit on the all-reduced set scores, as in the CLI.
+
+    gzip_on_device: a '.gz' out_format is compressed by every rank's GPU (FileTrimmer's option); the
+    parts and bin spans are whole gzip members, so the stitched files stay valid multi-member gzip.
 
     Returns the job's read counts (every rank). trimmer_factory(matching_sets, **options) builds
     the per-rank trimmer (FileTrimmer by default; the CPU tests pass an oracle-backed one)."""
@@ -422,6 +425,8 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
         opts.update(barcode_dir=bdir(rank), forward_or_reverse_barcodes=fwd_rev, barcode_threshold=barcode_threshold,
                     barcode_diff=barcode_diff, require_two_barcodes=require_two_barcodes, untrimmed=untrimmed,
                     discard_unassigned=discard_unassigned)
+    if gzip_on_device:
+        opts['gzip_on_device'] = True
     if trimmer_factory is None:
         from .pipeline import FileTrimmer
         trimmer_factory = FileTrimmer

@@ -610,7 +610,8 @@ int pcabi_kmer_approx_host(int device, const uint8_t *codes, int64_t codes_len, 
  *       start_trim / end_trim (NULL = untrimmed), middle cut ranges [cuts[2k], cuts[2k+1]) of the
  *       trimmed sequence for k in [cut_off[i], cut_off[i+1]) (NULL = none; a read with cuts is
  *       written as its split parts, or dropped with discard_middle), FASTA (70-column lines) or
- *       FASTQ, gzip when gz != 0, appended when append != 0, path "-" = stdout (plain only);
+ *       FASTQ, gzip when gz != 0 (2: compressed on the current device, see pcabi_reads_write_dev;
+ *       any other value: zlib), appended when append != 0, path "-" = stdout (plain only);
  *       untrimmed != 0 writes reads without cuts whole (split parts still come from the trimmed
  *       sequence, as in the reference). Returns the number of reads that produced output (the
  *       reference's non-empty read strings, porechop_abi.py:598-604), or a negative PCABI_E_*.
@@ -672,6 +673,58 @@ int pcabi_reads_write(const pcabi_reads *b, const char *path, int append, int gz
  * cache (PCABI_IO_CACHE_MB, default min(4 GB, RAM / 8)) for the next batch to reuse; this
  * returns every cached mapping to the system. */
 void pcabi_io_release_cache(void);
+/* pcabi_reads_write with gz = 2, "compress on the device", on device `gzip_device` (-1 = the
+ * calling thread's current device; pcabi_reads_write itself uses that for gz = 2). The records are
+ * laid out exactly as for a plain file, cut into blocks by pcabi_gzip_plan_lines (PCABI_GZIP_LONG_LINE,
+ * blocks up to 65535 bytes), compressed by pcabi_gzip_host and written or appended as gzip members:
+ * the file decompresses to the bytes gz = 0 writes. gz = 0 / 1 behave as in pcabi_reads_write. */
+int pcabi_reads_write_dev(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                          const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                          const int64_t *cuts, int min_split_read_size, int discard_middle,
+                          int untrimmed, const uint8_t *select, int gzip_device);
+/* Seconds the calling thread's last pcabi_reads_write / _dev call spent laying out the records (plain
+ * files and gz = 2), compressing on the device (gz = 2) and writing the file (tools/gz_timing.py). */
+void pcabi_reads_write_last_times(double *layout, double *compress, double *write);
+
+/* ---- gzip on the device (csrc/pcabi_deflate.hip) ----------------------------------------
+ * A gzip stream (RFC 1952 members of RFC 1951 blocks) of a byte buffer, compressed per block with
+ * no LZ77 matches: block k = bytes [block_off[k], block_off[k + 1]) (block_off[0] = 0,
+ * block_off[n_blocks] = n, every block 1..65535 bytes) becomes one dynamic-Huffman deflate block
+ * followed by an empty stored block (so the next block starts on a byte), or one stored block when
+ * that is not larger. block_off = NULL: fixed blocks of pcabi_gzip_block_len() bytes (n_blocks is
+ * ignored). Blocks are grouped into members, each with the CRC-32 (computed on the device) and
+ * ISIZE of its own bytes; the stream is multi-member, an empty input gives one empty member.
+ *   pcabi_gzip_bound        : capacity that always suffices (n_blocks = 0: fixed blocks).
+ *   pcabi_gzip_scratch_bytes: device scratch pcabi_gzip_dev needs.
+ *   pcabi_gzip_dev  : device pointers on the current device, asynchronous on `stream`, no host
+ *       synchronisation. *out_len (device) receives the stream length; when it exceeds cap nothing
+ *       is written to out; -1 (and nothing written) when the block list is not as described.
+ *       Returns 0 or a negative PCABI_E_*.
+ *   pcabi_gzip_host : host buffers (pageable), staged through pinned chunks so copies and kernels
+ *       overlap. Returns the stream length or a negative PCABI_E_* (a bad block list is refused
+ *       before anything is launched). When the length exceeds cap, out[cap..] is untouched and
+ *       out[0..cap) undefined: call again with the returned size. device -1 = current device.
+ *   pcabi_gzip_plan_lines : the writer's block list for text (host): a block never spans the end
+ *       of a line of long_line bytes or more, shorter lines are merged into neighbouring blocks up
+ *       to cap bytes, longer spans are cut evenly (long_line <= cap <= 65535). Writes
+ *       block_off[0 .. blocks] when blocks + 1 <= off_cap; returns the number of blocks.
+ *   pcabi_gzip_tune : test switches, process-wide: fixed block length, blocks per member, bytes per
+ *       staged pass of pcabi_gzip_host (0 = the default: 32768, 1024, 64 MiB).
+ *   pcabi_gzip_last_times : seconds the last pcabi_gzip_host call spent copying into pinned
+ *       memory, waiting for the device, and copying out of pinned memory.
+ */
+enum { PCABI_GZIP_LONG_LINE = 1024, PCABI_GZIP_BLOCK_CAP = 65535 };
+int pcabi_gzip_block_len(void);
+int64_t pcabi_gzip_bound(int64_t n, int64_t n_blocks);
+int64_t pcabi_gzip_scratch_bytes(int64_t n, int64_t n_blocks);
+int pcabi_gzip_tune(int block_len, int64_t member_blocks, int64_t chunk_bytes);
+int pcabi_gzip_dev(void *stream, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
+                   uint8_t *out, int64_t cap, int64_t *out_len, void *scratch, int64_t scratch_len);
+int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
+                        uint8_t *out, int64_t cap);
+int64_t pcabi_gzip_plan_lines(const char *text, int64_t n, int64_t long_line, int64_t cap, int64_t *block_off,
+                              int64_t off_cap);
+void pcabi_gzip_last_times(double *copy_in, double *wait, double *copy_out);
 
 #ifdef __cplusplus
 }
