@@ -133,6 +133,15 @@ def lib():
         'pcabi_gzip_plan_lines': ([c_p, c_i64, c_i64, c_i64, c_p, c_i64], c_i64),
         'pcabi_gzip_last_times': ([c_p, c_p, c_p], None),
         'pcabi_reads_write_last_times': ([c_p, c_p, c_p], None),
+        'pcabi_bgzf_bound': ([c_i64, c_i64, c_int], c_i64),
+        'pcabi_bgzf_host': ([c_int, c_p, c_i64, c_p, c_i64, c_int, c_p, c_i64], c_i64),
+        'pcabi_bgzf_write_eof': ([ctypes.c_char_p], c_int),
+        'pcabi_gunzip_index': ([c_p, c_i64, c_p, c_p, c_i64], c_i64),
+        'pcabi_gunzip_scratch_bytes': ([c_i64], c_i64),
+        'pcabi_gunzip_dev': ([c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64], c_int),
+        'pcabi_gunzip_host': ([c_int, c_p, c_i64, c_p, c_i64], c_i64),
+        'pcabi_gunzip_tune': ([c_i64], c_int),
+        'pcabi_gunzip_last_times': ([c_p, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -158,7 +167,7 @@ def exported_symbols():
             'pcabi_scan_destroy', 'pcabi_middle_scan_dev', 'pcabi_middle_scan_host', 'pcabi_middle_scan_seqs', 'pcabi_middle_seed_runs',
             'pcabi_middle_requeues', 'pcabi_scan_profile', 'pcabi_set_side_streams', 'pcabi_stream_side_streams',
             'pcabi_barcode_call_dev',
-            'pcabi_barcode_call_host', 'pcabi_fastx_open', 'pcabi_fastx_type', 'pcabi_fastx_next',
+            'pcabi_barcode_call_host', 'pcabi_fastx_open', 'pcabi_fastx_open_dev', 'pcabi_fastx_type', 'pcabi_fastx_next',
             'pcabi_fastx_close', 'pcabi_fastx_remaining', 'pcabi_fastx_load', 'pcabi_reads_count', 'pcabi_reads_type', 'pcabi_reads_views',
             'pcabi_reads_free', 'pcabi_reads_write', 'check_compatibility', 'pcabi_compat_host',
             'pcabi_compat_all_vs_all_host', 'pcabi_kmer_count_host', 'pcabi_kmer_top_host', 'pcabi_gather_host',
@@ -169,7 +178,10 @@ def exported_symbols():
             'pcabi_adapter_profile_dev', 'pcabi_adapter_profile_host', 'pcabi_reads_write_dev',
             'pcabi_gzip_block_len', 'pcabi_gzip_bound', 'pcabi_gzip_scratch_bytes', 'pcabi_gzip_tune', 'pcabi_gzip_dev',
             'pcabi_gzip_host', 'pcabi_gzip_plan_lines', 'pcabi_gzip_last_times',
-            'pcabi_reads_write_last_times']
+            'pcabi_reads_write_last_times',
+            'pcabi_gunzip_index', 'pcabi_gunzip_scratch_bytes', 'pcabi_gunzip_dev', 'pcabi_gunzip_host',
+            'pcabi_gunzip_tune', 'pcabi_gunzip_last_times', 'pcabi_bgzf_bound', 'pcabi_bgzf_host',
+            'pcabi_bgzf_write_eof']
 
 
 class CrossRegion(ctypes.Structure):

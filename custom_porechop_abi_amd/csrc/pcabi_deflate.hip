@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "../../include/pcabi.h"
+#include "pcabi_crc.h"
 #include "pcabi_deflate.h"
 
 namespace pcabi_internal {
@@ -38,6 +40,7 @@ int fail(int code, const std::string &msg);
 }
 using pcabi_internal::fail;
 using namespace pcabi_deflate;
+using namespace pcabi_crc;
 
 #define GZ_TRY(expr)                                                                        \
     do {                                                                                    \
@@ -51,42 +54,10 @@ constexpr int kThreads = 256;
 constexpr int kTile = 4096;          // bytes per workgroup step: 16 per lane
 constexpr int kTblStride = 260;      // uint32 per block: code | len << 16 for 257 symbols
 constexpr int kStageWords = 2048;    // 32 carry + 1880 header + 4096 * 15 + 57 tail bits < 65536
-constexpr uint32_t kPoly = 0xedb88320u;
 
 struct BlkInfo {
     uint32_t out_bytes, hdr_bits, crc, stored;
 };
-
-// a * b mod P, reflected representation (x^0 = 1 << 31), as zlib's multmodp
-__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ kPoly : b >> 1;
-    }
-    return p;
-}
-
-struct CrcTables {
-    uint32_t byte[256];     // the byte-wise CRC-32 table
-    uint32_t xp[4][256];    // xp[l][k] = x^(8 k 256^l) mod P
-};
-
-constexpr CrcTables make_tables() {
-    CrcTables t{};
-    for (uint32_t n = 0; n < 256; ++n) {
-        uint32_t c = n;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? kPoly ^ (c >> 1) : c >> 1;
-        t.byte[n] = c;
-    }
-    uint32_t step = 0x00800000u;   // x^8
-    for (int l = 0; l < 4; ++l) {
-        t.xp[l][0] = 0x80000000u;
-        for (int k = 1; k < 256; ++k) t.xp[l][k] = mulmod(t.xp[l][k - 1], step);
-        step = mulmod(t.xp[l][255], step);
-    }
-    return t;
-}
 
 __device__ const CrcTables d_tab = make_tables();
 
@@ -284,15 +255,16 @@ __global__ __launch_bounds__(kThreads) void k_plan(const uint8_t *__restrict__ i
     for (int i = tid; i < kHdrWords; i += kThreads) hdr[b * kHdrWords + i] = hbuf[i];
 }
 
-__device__ inline uint32_t member_extra_before(int64_t b, int64_t member_blocks) {
-    return b % member_blocks == 0 ? 10u : 0u;
+// hdr: bytes of a member's header, 10 (plain gzip) or 18 (BGZF: the BC subfield with the member's size)
+__device__ inline uint32_t member_extra_before(int64_t b, int64_t member_blocks, uint32_t hdr) {
+    return b % member_blocks == 0 ? hdr : 0u;
 }
 __device__ inline uint32_t member_extra_after(int64_t b, int64_t nb, int64_t member_blocks) {
     return (b % member_blocks == member_blocks - 1 || b == nb - 1) ? 10u : 0u;
 }
 
 __global__ __launch_bounds__(1024) void k_offsets(const BlkInfo *__restrict__ info, int64_t nb, int64_t member_blocks,
-                                                  int64_t cap, int64_t *__restrict__ out_off, int64_t *ctl,
+                                                  uint32_t hdr, int64_t cap, int64_t *__restrict__ out_off, int64_t *ctl,
                                                   int64_t *out_len) {
     __shared__ uint32_t wsum[16];
     int64_t carry = 0;
@@ -300,7 +272,7 @@ __global__ __launch_bounds__(1024) void k_offsets(const BlkInfo *__restrict__ in
         const int64_t b = base + threadIdx.x;
         uint32_t s = 0, pre = 0;
         if (b < nb) {
-            pre = member_extra_before(b, member_blocks);
+            pre = member_extra_before(b, member_blocks, hdr);
             s = info[b].out_bytes + pre + member_extra_after(b, nb, member_blocks);
         }
         uint32_t total = 0;
@@ -309,7 +281,7 @@ __global__ __launch_bounds__(1024) void k_offsets(const BlkInfo *__restrict__ in
         carry += total;
     }
     if (threadIdx.x == 0) {
-        const int64_t total = nb == 0 ? kMemberOverhead : carry;
+        const int64_t total = nb == 0 ? (hdr == 18 ? 0 : kMemberOverhead) : carry;   // BGZF: no member for no bytes
         const bool bad = ctl[0] != 0;
         ctl[1] = bad ? -1 : total;
         ctl[2] = (bad || total > cap) ? 1 : 0;
@@ -326,7 +298,7 @@ __device__ inline void put_le32(uint8_t *p, uint32_t v) {
 }
 
 __global__ __launch_bounds__(kThreads) void k_members(const int64_t *__restrict__ block_off, int64_t nb, int64_t fixed,
-                                                      int64_t n, int64_t member_blocks,
+                                                      int64_t n, int64_t member_blocks, uint32_t hdr,
                                                       const BlkInfo *__restrict__ info,
                                                       const int64_t *__restrict__ out_off, const int64_t *ctl,
                                                       uint8_t *__restrict__ out) {
@@ -354,10 +326,16 @@ __global__ __launch_bounds__(kThreads) void k_members(const int64_t *__restrict_
     if ((tid & 63) == 0) atomicXor(&s_crc, acc);
     __syncthreads();
     if (tid == 0) {
-        uint8_t *h = out + (last > first ? out_off[first] - 10 : 0);
-        uint8_t *t = last > first ? out + out_off[last - 1] + info[last - 1].out_bytes : h + 10;
+        uint8_t *h = out + (last > first ? out_off[first] - hdr : 0);
+        uint8_t *t = last > first ? out + out_off[last - 1] + info[last - 1].out_bytes : h + hdr;
         const uint8_t head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
         for (int i = 0; i < 10; ++i) h[i] = head[i];
+        if (hdr == 18) {   // BGZF: FEXTRA, XLEN 6, "BC", SLEN 2, BSIZE = member bytes - 1
+            const uint32_t bsize = (uint32_t)(t + 10 - h) - 1u;
+            const uint8_t x[8] = {6, 0, 0x42, 0x43, 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8)};
+            h[3] = 4;
+            for (int i = 0; i < 8; ++i) h[10 + i] = x[i];
+        }
         t[0] = 0x03;   // BFINAL 1, fixed Huffman, end-of-block
         t[1] = 0x00;
         put_le32(t + 2, s_crc);
@@ -485,10 +463,14 @@ int64_t scratch_bytes(int64_t nb) {
 }
 
 int64_t bound(int64_t n, int64_t nb) { return n + 25 * nb + kMemberOverhead + 16; }
+constexpr int64_t kBgzfBlockCap = PCABI_BGZF_BLOCK_CAP;   // a stored block + 28 bytes of member stay within 65536
+constexpr int64_t kBgzfEofBytes = 28;
+// one member per block: 18 header + 5 stored (or less) + 2 closing block + 8 trailer
+int64_t bgzf_bound(int64_t n, int64_t nb, int eof) { return n + 33 * nb + (eof ? kBgzfEofBytes : 0) + 16; }
 
 // queues the four kernels; out_len_dev receives the stream length, or -1 for a bad block list
 int launch(hipStream_t st, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t nb, int64_t fixed,
-           int64_t member_blocks, uint8_t *out, int64_t cap, int64_t *out_len_dev, void *scratch) {
+           int64_t member_blocks, uint32_t mhdr, uint8_t *out, int64_t cap, int64_t *out_len_dev, void *scratch) {
     char *p = (char *)scratch;
     int64_t *ctl = (int64_t *)p;
     p += 64;
@@ -501,10 +483,11 @@ int launch(hipStream_t st, const uint8_t *in, int64_t n, const int64_t *block_of
     uint32_t *tbl = (uint32_t *)p;
     GZ_TRY(hipMemsetAsync(ctl, 0, 64, st));
     if (nb > 0) hipLaunchKernelGGL(k_plan, dim3((unsigned)nb), dim3(kThreads), 0, st, in, n, block_off, nb, fixed, tbl, hdr, info, ctl);
-    hipLaunchKernelGGL(k_offsets, dim3(1), dim3(1024), 0, st, info, nb, member_blocks, cap, out_off, ctl, out_len_dev);
+    hipLaunchKernelGGL(k_offsets, dim3(1), dim3(1024), 0, st, info, nb, member_blocks, mhdr, cap, out_off, ctl, out_len_dev);
     const int64_t nm = std::max<int64_t>(1, (nb + member_blocks - 1) / member_blocks);
-    hipLaunchKernelGGL(k_members, dim3((unsigned)nm), dim3(kThreads), 0, st, block_off, nb, fixed, n, member_blocks, info,
-                       out_off, ctl, out);
+    if (nb > 0 || mhdr != 18)
+        hipLaunchKernelGGL(k_members, dim3((unsigned)nm), dim3(kThreads), 0, st, block_off, nb, fixed, n, member_blocks, mhdr,
+                           info, out_off, ctl, out);
     if (nb > 0)
         hipLaunchKernelGGL(k_encode, dim3((unsigned)nb), dim3(kThreads), 0, st, in, n, block_off, nb, fixed, tbl, hdr, info,
                            out_off, ctl, out);
@@ -574,7 +557,7 @@ int stage_reserve(int device, int64_t bytes, int64_t blocks) {
     g_stage.device = device;
     g_stage.bytes = bytes;
     g_stage.blocks = blocks;
-    const size_t ob = (size_t)bound(bytes, blocks);
+    const size_t ob = (size_t)std::max(bound(bytes, blocks), bgzf_bound(bytes, blocks, 0));
     for (Slot &s : g_stage.s) {
         GZ_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
         GZ_TRY(hipHostMalloc((void **)&s.pin_in, (size_t)bytes + 16, hipHostMallocDefault));
@@ -634,14 +617,17 @@ int pcabi_gzip_dev(void *stream, const uint8_t *in, int64_t n, const int64_t *bl
     else if ((n > 0) != (n_blocks > 0)) return fail(PCABI_E_ARG, "a block list must cover the input");
     if (n_blocks > INT32_MAX) return fail(PCABI_E_ARG, "too many blocks for one call");
     if (scratch_len < scratch_bytes(n_blocks)) return fail(PCABI_E_ARG, "scratch smaller than pcabi_gzip_scratch_bytes");
-    return launch((hipStream_t)stream, in, n, block_off, n_blocks, fixed, g_member_blocks, out, cap, out_len, scratch);
+    return launch((hipStream_t)stream, in, n, block_off, n_blocks, fixed, g_member_blocks, 10, out, cap, out_len, scratch);
 }
 
-int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
-                        uint8_t *out, int64_t cap) {
+static int64_t gzip_host_impl(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
+                              uint8_t *out, int64_t cap, bool bgzf) {
     if (n < 0 || n_blocks < 0 || cap < 0 || (n > 0 && !in) || (cap > 0 && !out)) return fail(PCABI_E_ARG, "bad arguments");
     std::lock_guard<std::mutex> lk(g_stage_mu);
-    const int64_t fixed = g_block_len, member_blocks = g_member_blocks, chunk = g_chunk_bytes;
+    const int64_t block_cap = bgzf ? kBgzfBlockCap : kBlockCap;
+    const int64_t fixed = std::min<int64_t>(g_block_len, block_cap), member_blocks = bgzf ? 1 : g_member_blocks,
+                  chunk = g_chunk_bytes;
+    const uint32_t hdr = bgzf ? 18 : 10;
     // passes: [first block, last block) each, whole members
     std::vector<int64_t> pass{0};
     int64_t max_bytes = 0, max_blocks = 0;
@@ -650,7 +636,8 @@ int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t 
             return fail(PCABI_E_ARG, "a block list starts at 0, ends at n and covers the input");
         for (int64_t b = 0; b < n_blocks; ++b) {
             const int64_t l = block_off[b + 1] - block_off[b];
-            if (l < 1 || l > kBlockCap) return fail(PCABI_E_ARG, "every block holds 1..65535 bytes");
+            if (l < 1 || l > block_cap)
+                return fail(PCABI_E_ARG, bgzf ? "every BGZF block holds 1..65280 bytes" : "every block holds 1..65535 bytes");
         }
         int64_t first = 0;
         for (int64_t b = 0; b < n_blocks; ++b)
@@ -690,8 +677,9 @@ int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t 
             if (bytes > 0) GZ_TRY(hipMemcpyAsync(s.dev_in, s.pin_in, (size_t)bytes, hipMemcpyHostToDevice, s.st));
             if (block_off)
                 GZ_TRY(hipMemcpyAsync(s.dev_off, s.pin_off, 8 * (size_t)(b1 - b0 + 1), hipMemcpyHostToDevice, s.st));
-            if (int rc = launch(s.st, s.dev_in, bytes, block_off ? s.dev_off : nullptr, b1 - b0, fixed, member_blocks,
-                                s.dev_out, bound(bytes, b1 - b0), s.dev_len, s.scratch))
+            if (int rc = launch(s.st, s.dev_in, bytes, block_off ? s.dev_off : nullptr, b1 - b0, fixed, member_blocks, hdr,
+                                s.dev_out, bgzf ? bgzf_bound(bytes, b1 - b0, 0) : bound(bytes, b1 - b0), s.dev_len,
+                                s.scratch))
                 return rc;
             GZ_TRY(hipMemcpyAsync(s.pin_len, s.dev_len, 8, hipMemcpyDeviceToHost, s.st));
         }
@@ -717,6 +705,39 @@ int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t 
         }
     }
     return total;
+}
+
+int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
+                        uint8_t *out, int64_t cap) {
+    return gzip_host_impl(device, in, n, block_off, n_blocks, out, cap, false);
+}
+
+static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+int64_t pcabi_bgzf_bound(int64_t n, int64_t n_blocks, int eof) {
+    if (n < 0 || n_blocks < 0) return fail(PCABI_E_ARG, "negative size");
+    const int64_t fixed = std::min<int64_t>(g_block_len, kBgzfBlockCap);
+    if (n_blocks == 0) n_blocks = (n + fixed - 1) / fixed;
+    return bgzf_bound(n, n_blocks, eof);
+}
+
+int64_t pcabi_bgzf_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks, int eof,
+                        uint8_t *out, int64_t cap) {
+    const int64_t tail = eof ? kBgzfEofBytes : 0;
+    if (cap < 0) return fail(PCABI_E_ARG, "bad arguments");
+    const int64_t zn = gzip_host_impl(device, in, n, block_off, n_blocks, out, std::max<int64_t>(cap - tail, 0), true);
+    if (zn < 0) return zn;
+    if (tail && zn + tail <= cap) std::memcpy(out + zn, kBgzfEof, (size_t)tail);
+    return zn + tail;
+}
+
+int pcabi_bgzf_write_eof(const char *path) {
+    if (!path) return fail(PCABI_E_ARG, "bad arguments");
+    FILE *f = std::fopen(path, "ab");
+    if (!f) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+    const bool ok = std::fwrite(kBgzfEof, 1, sizeof kBgzfEof, f) == sizeof kBgzfEof;
+    if (std::fclose(f) != 0 || !ok) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+    return 0;
 }
 
 // seconds the last pcabi_gzip_host call spent copying into pinned memory, waiting for the device

@@ -78,8 +78,19 @@ const bool g_dna5_init = [] {
 
 }  // namespace
 
+namespace pcabi_internal {
+// the device source of a block-gzipped input (csrc/pcabi_inflate.hip)
+struct GunzipReader;
+int gunzip_reader_open(const uint8_t *z, int64_t n, int device, GunzipReader **out);
+int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room);
+void gunzip_reader_close(GunzipReader *g);
+}  // namespace pcabi_internal
+
 struct pcabi_fastx {
     gzFile f = nullptr;
+    pcabi_internal::GunzipReader *dev = nullptr;   // block-gzipped input inflated on the device, instead of f
+    void *zmap = nullptr;                          // its compressed bytes, mapped whole
+    size_t zmap_len = 0;
     int type = -1;                 // PCABI_FASTA / PCABI_FASTQ
     std::vector<char> buf;         // gzip: decoded bytes [0, end)
     const char *base = nullptr;    // buf.data(), or the mapping of a plain file
@@ -304,13 +315,26 @@ bool next_line(pcabi_fastx *r, const char **p, size_t *n) {
         }
         if (r->buf.size() - r->end < (1u << 20)) r->buf.resize(std::max<size_t>(r->buf.size() * 2, 4u << 20));
         r->base = r->buf.data();
-        const int got = gzread(r->f, r->buf.data() + r->end, (unsigned)std::min<size_t>(r->buf.size() - r->end, 1u << 30));
-        int zerr = Z_OK;
-        const char *zmsg = got < 0 || got == 0 ? gzerror(r->f, &zerr) : nullptr;
-        if (got < 0 || (got == 0 && zerr != Z_OK && zerr != Z_STREAM_END)) {
+        const size_t room = std::min<size_t>(r->buf.size() - r->end, 1u << 30);
+        int got;
+        const char *zmsg = nullptr;
+        bool bad;
+        if (r->dev) {
+            const int64_t k = pcabi_internal::gunzip_reader_read(r->dev, r->buf.data() + r->end, (int64_t)room);
+            got = k < 0 ? -1 : (int)k;
+            bad = k < 0;
+            if (bad) zmsg = pcabi_last_error();
+        } else {
+            got = gzread(r->f, r->buf.data() + r->end, (unsigned)room);
+            int zerr = Z_OK;
+            zmsg = got < 0 || got == 0 ? gzerror(r->f, &zerr) : nullptr;
+            bad = got < 0 || (got == 0 && zerr != Z_OK && zerr != Z_STREAM_END);
+        }
+        if (bad) {
             // a damaged or truncated gzip stream: the reference's gzip module raises too
             // (EOFError "Compressed file ended before the end-of-stream marker was reached")
-            fail(PCABI_E_PARSE, std::string("read error: ") + (zmsg ? zmsg : "?"));
+            const std::string msg = std::string("read error: ") + (zmsg ? zmsg : "?");
+            fail(PCABI_E_PARSE, msg);
             r->err = true;
             r->eof = true;
             r->end = r->pos;   // drop the partial data
@@ -525,7 +549,7 @@ void fill_fastq(pcabi_reads *b, const char *T, const std::vector<Span> &rec, boo
 
 extern "C" {
 
-int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) {
+static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **out) {
     if (!path || !out) return fail(PCABI_E_ARG, "bad arguments");
     *out = nullptr;
     FILE *fp = std::fopen(path, "rb");
@@ -560,7 +584,30 @@ int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) {
         }
         if (fd >= 0) ::close(fd);
     }
-    if (!r->map) {
+    if (gz && device >= 0) {
+        // block-gzipped (every member lists its size): map the compressed file, index it, inflate
+        // group by group on the device. Anything else falls through to zlib.
+        const int fd = ::open(path, O_RDONLY);
+        struct stat st;
+        if (fd >= 0 && fstat(fd, &st) == 0 && st.st_size > 0) {
+            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) {
+                const int rc = pcabi_internal::gunzip_reader_open((const uint8_t *)m, (int64_t)st.st_size, device, &r->dev);
+                if (rc < 0 || !r->dev) munmap(m, (size_t)st.st_size);
+                if (rc < 0) {
+                    ::close(fd);
+                    delete r;
+                    return rc;
+                }
+                if (r->dev) {
+                    r->zmap = m;
+                    r->zmap_len = (size_t)st.st_size;
+                }
+            }
+        }
+        if (fd >= 0) ::close(fd);
+    }
+    if (!r->map && !r->dev) {
         gzFile f = gzopen(path, "rb");
         if (!f) {
             delete r;
@@ -580,7 +627,12 @@ int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) {
         r->base = r->buf.data();
         // type from the first decoded character
         while (r->end == 0 && !r->eof) {
-            const int got = gzread(r->f, r->buf.data(), (unsigned)r->buf.size());
+            const int64_t got = r->dev ? pcabi_internal::gunzip_reader_read(r->dev, r->buf.data(), (int64_t)r->buf.size())
+                                       : (int64_t)gzread(r->f, r->buf.data(), (unsigned)r->buf.size());
+            if (got < 0 && r->dev) {   // a member that does not inflate, or a device error: not "no type"
+                pcabi_fastx_close(r);
+                return (int)got;
+            }
             if (got <= 0) r->eof = true;
             else r->end = (size_t)got;
         }
@@ -594,6 +646,12 @@ int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) {
     }
     *out = r;
     return 0;
+}
+
+int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) { return fastx_open_impl(path, raw, -1, out); }
+
+int pcabi_fastx_open_dev(const char *path, int raw, int device, pcabi_fastx **out) {
+    return fastx_open_impl(path, raw, device, out);
 }
 
 int pcabi_fastx_type(const pcabi_fastx *r) { return r ? r->type : -1; }
@@ -680,6 +738,8 @@ int pcabi_fastx_set_range(pcabi_fastx *r, int64_t begin, int64_t end) {
 void pcabi_fastx_close(pcabi_fastx *r) {
     if (!r) return;
     if (r->f) gzclose(r->f);
+    if (r->dev) pcabi_internal::gunzip_reader_close(r->dev);
+    if (r->zmap) munmap(r->zmap, r->zmap_len);
     r->ahead_stop = true;                 // the populate-ahead helper leaves the mapping first
     if (r->ahead.joinable()) r->ahead.join();
     if (r->map) {
@@ -1111,7 +1171,8 @@ static double wall_s() {
 static int reads_write_impl(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
                             const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
                             const int64_t *cuts, int min_split_read_size, int discard_middle,
-                            int untrimmed, const uint8_t *select, int gzip_device) {
+                            int untrimmed, const uint8_t *select, int gzip_device, bool bgzf) {
+    // bgzf (with gz = 2): one indexed BGZF member per block of at most 65280 bytes, no end marker
     if (!b || !path) return fail(PCABI_E_ARG, "bad arguments");
     if (gz == 2 && std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "gz = 2 writes files, not stdout");
     Sink o;
@@ -1240,7 +1301,8 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
             emit[(size_t)t] = e;
             if (gz == 2)
                 pcabi_deflate::plan_blocks(out.data(), bytes[(size_t)t], bytes[(size_t)t + 1], PCABI_GZIP_LONG_LINE,
-                                           PCABI_GZIP_BLOCK_CAP, [&](int64_t end) { ends[(size_t)t].push_back(end); });
+                                           bgzf ? (int64_t)PCABI_BGZF_BLOCK_CAP : (int64_t)PCABI_GZIP_BLOCK_CAP,
+                                           [&](int64_t end) { ends[(size_t)t].push_back(end); });
         });
         for (int t = 0; t < nt; ++t) emitted += emit[(size_t)t];
         g_write_times[0] = wall_s() - t_begin;
@@ -1258,10 +1320,13 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
         for (const auto &v : ends) block_off.insert(block_off.end(), v.begin(), v.end());
         const int64_t nblk = (int64_t)block_off.size() - 1;
         std::vector<uint8_t, NoInit<uint8_t>> z;
-        z.resize((size_t)pcabi_gzip_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1)));
+        z.resize((size_t)(bgzf ? pcabi_bgzf_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1), 0)
+                               : pcabi_gzip_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1))));
         const double t0 = wall_s();
-        const int64_t zn = pcabi_gzip_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
-                                           block_off.data(), nblk, z.data(), (int64_t)z.size());
+        const int64_t zn = bgzf ? pcabi_bgzf_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
+                                                  block_off.data(), nblk, 0, z.data(), (int64_t)z.size())
+                                : pcabi_gzip_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
+                                                  block_off.data(), nblk, z.data(), (int64_t)z.size());
         g_write_times[1] = wall_s() - t0;
         if (zn < 0 || zn > (int64_t)z.size()) {
             ::close(o.fd);
@@ -1285,15 +1350,15 @@ extern "C" int pcabi_reads_write(const pcabi_reads *b, const char *path, int app
                                  const int64_t *cuts, int min_split_read_size, int discard_middle,
                                  int untrimmed, const uint8_t *select) {
     return reads_write_impl(b, path, append, gz, fasta, start_trim, end_trim, cut_off, cuts, min_split_read_size,
-                            discard_middle, untrimmed, select, -1);
+                            discard_middle, untrimmed, select, -1, false);
 }
 
 extern "C" int pcabi_reads_write_dev(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
                                      const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
                                      const int64_t *cuts, int min_split_read_size, int discard_middle,
                                      int untrimmed, const uint8_t *select, int gzip_device) {
-    return reads_write_impl(b, path, append, gz, fasta, start_trim, end_trim, cut_off, cuts, min_split_read_size,
-                            discard_middle, untrimmed, select, gzip_device);
+    return reads_write_impl(b, path, append, gz == 3 ? 2 : gz, fasta, start_trim, end_trim, cut_off, cuts,
+                            min_split_read_size, discard_middle, untrimmed, select, gzip_device, gz == 3);
 }
 
 extern "C" void pcabi_reads_write_last_times(double *layout, double *compress, double *write) {

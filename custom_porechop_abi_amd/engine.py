@@ -683,3 +683,64 @@ def gzip_compress(data, blocks=None, device=0, cap=None):
     if n > size:
         raise ValueError('gzip_compress: capacity %d, needed %d' % (size, n))
     return out[:n].tobytes()
+
+
+# ---- gunzip on the device (csrc/pcabi_inflate.hip) -----------------------------------------------
+BGZF_BLOCK_CAP = 65280    # include/pcabi.h PCABI_BGZF_BLOCK_CAP
+BGZF_MEMBER_MAX = 65536   # include/pcabi.h PCABI_BGZF_MEMBER_MAX
+BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
+
+
+def bgzf_compress(data, blocks=None, device=0, eof=True, cap=None):
+    """data as a BGZF stream compressed on GPU `device` (pcabi_bgzf_host): one indexed gzip member per
+    block (blocks: block_off[n_blocks + 1], every block 1..65280 bytes; None: fixed blocks of
+    min(gzip_block_len(), 65280)), the 28-byte end-of-file member after them when eof. Returns bytes."""
+    buf, off = _gzip_input(data, blocks)
+    L = lib()
+    nb = 0 if off is None else off.size - 1
+    size = int(L.pcabi_bgzf_bound(buf.size, nb, int(bool(eof)))) if cap is None else int(cap)
+    out = np.empty(max(size, 1), np.uint8)
+    n = L.pcabi_bgzf_host(int(device), _ptr(buf), buf.size, None if off is None else _ptr(off), nb, int(bool(eof)),
+                          _ptr(out), size)
+    if n < 0:
+        check(int(n), 'pcabi_bgzf_host')
+    if n > size:
+        raise ValueError('bgzf_compress: capacity %d, needed %d' % (size, n))
+    return out[:n].tobytes()
+
+
+def bgzf_index(data):
+    """The members of a block-gzipped (BGZF) stream, listed from their headers without decoding
+    (pcabi_gunzip_index): (in_off, out_off), int64 arrays of members + 1 entries (member starts and
+    the prefix sums of the decoded sizes), or None when the stream is gzip but not indexable.
+    A broken or truncated chain raises PcabiError."""
+    buf, _ = _gzip_input(data, None)
+    L = lib()
+    m = L.pcabi_gunzip_index(_ptr(buf), buf.size, None, None, 0)
+    if m < 0:
+        check(int(m), 'pcabi_gunzip_index')
+    if m == 0:
+        return None
+    in_off, out_off = np.zeros(m + 1, np.int64), np.zeros(m + 1, np.int64)
+    L.pcabi_gunzip_index(_ptr(buf), buf.size, _ptr(in_off), _ptr(out_off), m + 1)
+    return in_off, out_off
+
+
+def gunzip(data, device=0, cap=None):
+    """A block-gzipped stream inflated on GPU `device` (pcabi_gunzip_host). Returns bytes. A stream
+    that is not indexable, or a member that does not inflate, raises PcabiError. cap (tests): the
+    output capacity offered; a too small one raises ValueError naming the size needed."""
+    buf, _ = _gzip_input(data, None)
+    L = lib()
+    if cap is None:
+        idx = bgzf_index(buf)
+        size = 0 if idx is None else int(idx[1][-1])
+    else:
+        size = int(cap)
+    out = np.empty(max(size, 1), np.uint8)
+    n = L.pcabi_gunzip_host(int(device), _ptr(buf), buf.size, _ptr(out), size)
+    if n < 0:
+        check(int(n), 'pcabi_gunzip_host')
+    if n > size:
+        raise ValueError('gunzip: capacity %d, needed %d' % (size, n))
+    return out[:n].tobytes()

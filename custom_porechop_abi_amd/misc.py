@@ -38,6 +38,7 @@ def _declare(L):
     P, i64, c_int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     sig = {
         'pcabi_fastx_open': ([ctypes.c_char_p, c_int, ctypes.POINTER(P)], c_int),
+        'pcabi_fastx_open_dev': ([ctypes.c_char_p, c_int, c_int, ctypes.POINTER(P)], c_int),
         'pcabi_fastx_type': ([P], c_int),
         'pcabi_fastx_next': ([P, i64, i64, ctypes.POINTER(P)], i64),
         'pcabi_fastx_close': ([P], None),
@@ -49,6 +50,7 @@ def _declare(L):
         'pcabi_reads_write': ([P, ctypes.c_char_p, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P], c_int),
         'pcabi_reads_write_dev': ([P, ctypes.c_char_p, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P, c_int],
                                   c_int),
+        'pcabi_bgzf_write_eof': ([ctypes.c_char_p], c_int),
         'pcabi_fastx_record_start': ([P, i64], i64),
         'pcabi_fastx_set_range': ([P, i64, i64], c_int),
         'pcabi_fastx_remaining': ([P], i64),
@@ -221,6 +223,35 @@ def record_boundaries(path, parts):
         L.pcabi_fastx_close(h)
 
 
+def _starts_bgzf(path):
+    """Whether the file's first gzip member carries the BGZF 'BC' subfield. Anything else (a plain
+    file, ordinary gzip) keeps the loader it always had, whatever gunzip_device says."""
+    try:
+        with open(path, 'rb') as f:
+            h = f.read(12)
+            if len(h) < 12 or h[:3] != b'\x1f\x8b\x08' or not h[3] & 4:
+                return False
+            extra = f.read(h[10] | h[11] << 8)
+    except OSError:
+        return False
+    q = 0
+    while q + 4 <= len(extra):
+        slen = extra[q + 2] | extra[q + 3] << 8
+        if extra[q:q + 2] == b'BC' and slen == 2:
+            return True
+        q += 4 + slen
+    return False
+
+
+def _fastx_open(L, path, raw, gunzip_device):
+    """pcabi_fastx_open, or pcabi_fastx_open_dev when gunzip_device names a GPU (a block-gzipped file
+    is then inflated there; any other file reads as before). Returns (rc, handle)."""
+    h = ctypes.c_void_p()
+    if gunzip_device is None:
+        return L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h)), h
+    return L.pcabi_fastx_open_dev(os.fsencode(path), int(raw), int(gunzip_device), ctypes.byref(h)), h
+
+
 def ramp_sizes(max_reads, remaining_reads=None, done=0):
     """The next batch's read count for a pipeline's ramp (misc.read_batches ramp=True): batches
     grow from max_reads / 8 by doubling (the later stages start after a small first parse) and,
@@ -235,16 +266,16 @@ def ramp_sizes(max_reads, remaining_reads=None, done=0):
 
 
 def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_range=None, first_reads=None,
-                 ramp=False):
+                 ramp=False, gunzip_device=None):
     """Stream a FASTA / FASTQ(.gz) file as ReadBatch objects (pcabi_fastx_next); byte_range =
     (begin, end) record starts of a plain file (record_boundaries) reads only that range;
     first_reads: the first batch's size, if other than max_reads (a pipeline starts its later
     stages sooner on a small first batch); ramp: batch sizes from ramp_sizes (a plain file's last
     batches shrink too, from the bytes left and the bytes per read so far). Batching never changes
-    what is read or written, only when."""
+    what is read or written, only when. gunzip_device: a GPU that inflates a block-gzipped (BGZF)
+    input (pcabi_fastx_open_dev); None reads every gzip input with zlib."""
     L = _declare(lib())
-    h = ctypes.c_void_p()
-    rc = L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h))
+    rc, h = _fastx_open(L, path, raw, gunzip_device)
     if rc != 0:
         raise ValueError(_open_error(path))
     if byte_range is not None and L.pcabi_fastx_set_range(h, int(byte_range[0]), int(byte_range[1])) != 0:
@@ -277,13 +308,13 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
         L.pcabi_fastx_close(h)
 
 
-def text_chunks(path, chunk_bytes):
+def text_chunks(path, chunk_bytes, gunzip_device=None):
     """Stream a FASTA / FASTQ(.gz) file as spans of its decoded text holding whole records, cut
     where a fresh reader parses the same records (pcabi_fastx_next_text): yields memoryviews of at
-    least chunk_bytes (the last may be shorter), each valid until the next one is requested."""
+    least chunk_bytes (the last may be shorter), each valid until the next one is requested.
+    gunzip_device: as in read_batches."""
     L = _declare(lib())
-    h = ctypes.c_void_p()
-    rc = L.pcabi_fastx_open(os.fsencode(path), 0, ctypes.byref(h))
+    rc, h = _fastx_open(L, path, 0, gunzip_device)
     if rc != 0:
         raise ValueError(_open_error(path))
     try:
@@ -299,10 +330,21 @@ def text_chunks(path, chunk_bytes):
         L.pcabi_fastx_close(h)
 
 
-def load_batch(path, raw=False):
-    """The whole file as one ReadBatch (pcabi_fastx_load); raw keeps the file's own text."""
+def load_batch(path, raw=False, gunzip_device=None):
+    """The whole file as one ReadBatch (pcabi_fastx_load); raw keeps the file's own text.
+    gunzip_device: a GPU that inflates a block-gzipped (BGZF) input (pcabi_fastx_open_dev)."""
     L = _declare(lib())
     b = ctypes.c_void_p()
+    if gunzip_device is not None and _starts_bgzf(path):
+        rc, h = _fastx_open(L, path, raw, gunzip_device)
+        if rc != 0:
+            raise ValueError(_open_error(path))
+        try:
+            if L.pcabi_fastx_next(h, (1 << 63) - 1, (1 << 63) - 1, ctypes.byref(b)) < 0:
+                raise ValueError(_open_error(path))
+        finally:
+            L.pcabi_fastx_close(h)
+        return ReadBatch(b)
     rc = L.pcabi_fastx_load(os.fsencode(path), int(raw), ctypes.byref(b))
     if rc != 0:
         raise ValueError(_open_error(path))
@@ -418,11 +460,14 @@ def get_albacore_barcode_from_path(albacore_path):
 
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
-                cut_arrays=None, gzip_device=None):
+                cut_arrays=None, gzip_device=None, bgzf=False):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
     gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
-    that GPU (pcabi_reads_write_dev, gz = 2: a multi-member gzip file of the same text).
+    that GPU (pcabi_reads_write_dev, gz = 2: a multi-member gzip file of the same text). bgzf (with
+    gzip_device): gz = 3, one indexed BGZF member per block of at most 65280 bytes, which bgzip,
+    htslib and this project's device reader take member by member; the end-of-file marker is not
+    written, so batches can be appended: bgzf_finish(path) closes the file.
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -449,8 +494,10 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
         cu = np.array(flat if flat else [0, 0], np.int64)
     sel = None if select is None else np.ascontiguousarray(select, np.uint8)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+    if bgzf and not (gz and gzip_device is not None):
+        raise ValueError("bgzf applies to a '.gz' format compressed on a device (gzip_device)")
     if gz and gzip_device is not None:
-        rc = L.pcabi_reads_write_dev(batch._h, os.fsencode(path), int(append), 2, int(fasta), p(st), p(et), p(co),
+        rc = L.pcabi_reads_write_dev(batch._h, os.fsencode(path), int(append), 3 if bgzf else 2, int(fasta), p(st), p(et), p(co),
                                      p(cu), int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel),
                                      int(gzip_device))
     else:
@@ -459,6 +506,13 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     if rc < 0:
         check(rc, 'pcabi_reads_write')
     return int(rc)
+
+
+def bgzf_finish(path):
+    """Append the 28-byte BGZF end-of-file marker to a file written with write_reads(bgzf=True)
+    (pcabi_bgzf_write_eof)."""
+    L = _declare(lib())
+    check(L.pcabi_bgzf_write_eof(os.fsencode(path)), 'pcabi_bgzf_write_eof')
 
 
 def positions_to_ranges(positions):

@@ -29,6 +29,13 @@ from .porechop_abi import middle_adapter_list
 VP = ctypes.c_void_p
 
 
+def _bgzf_mode(trimmer, out_format):
+    """Whether this trimmer writes out_format as BGZF: the option, a '.gz' format, the device encoder
+    (trim_file also serves trimmers that are not FileTrimmers and know none of these)."""
+    return bool(getattr(trimmer, 'bgzf', False)) and out_format.endswith('.gz') and \
+        getattr(trimmer, 'gzip_device', None) is not None
+
+
 class FileTrimmer(object):
     """Device state for trimming batches against one list of matching adapter sets.
 
@@ -39,17 +46,27 @@ class FileTrimmer(object):
 
     barcode_dir = None                    # -b off (set by __init__)
     gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
+    bgzf = False                          # device-compressed '.gz' output as plain multi-member gzip
+    gunzip_device = None                  # gzip inputs through zlib on the host (set by __init__)
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
                  extra_middle_trim_bad_side=100, min_split_read_size=1000, no_split=False, discard_middle=False,
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
-                 discard_unassigned=False, gzip_on_device=False):
+                 discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False):
         self.L = L = lib()
         self.device = int(device)
         # '.gz' output formats: zlib on the host (default) or the device encoder (misc.write_reads)
         self.gzip_device = self.device if gzip_on_device else None
+        # with gzip_on_device: '.gz' output as indexed BGZF members (misc.write_reads bgzf), every
+        # file the run wrote (bins included) finished with the end-of-file marker
+        if bgzf and not gzip_on_device:
+            raise ValueError('bgzf needs gzip_on_device=True')
+        self.bgzf = bool(bgzf)
+        # block-gzipped (BGZF) inputs: zlib on the host (default) or inflated on the device by the reader
+        # thread (misc.read_batches gunzip_device); any other input reads as before
+        self.gunzip_device = self.device if gunzip_on_device else None
         check(L.pcabi_dev_set(device), 'pcabi_dev_set')
         self.sc = tuple(int(x) for x in scoring_scheme_vals[:4])
         self.E, self.thr, self.extra, self.min_trim = int(end_size), float(end_threshold), int(extra_end_trim), \
@@ -280,11 +297,14 @@ class FileTrimmer(object):
             for f, alb in files:
                 # batch sizes ramp up at the start and down at the end (misc.ramp_sizes): the first
                 # parse and the last write are small, so they overlap the other stages
-                for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True):
+                for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True,
+                                           gunzip_device=getattr(self, 'gunzip_device', None)):
                     yield b, alb
 
         def produce():
             try:
+                if getattr(self, 'gunzip_device', None) is not None:
+                    check(self.L.pcabi_dev_set(self.device), 'pcabi_dev_set')   # this thread's own device
                 items = iter(source if source is not None else
                              ((k, b, alb) for k, (b, alb) in enumerate(batches())))
                 while True:
@@ -323,7 +343,8 @@ class FileTrimmer(object):
                         at = os.path.getsize(out_path) if (segments is not None and not first) else 0
                         misc.write_reads(b, out_path, out_format, st, et, None, self.min_split, self.discard_middle,
                                          select=keep, append=not first, cut_arrays=(co, cu),
-                                         gzip_device=getattr(self, 'gzip_device', None))
+                                         gzip_device=getattr(self, 'gzip_device', None),
+                                         bgzf=_bgzf_mode(self, out_format))
                         if segments is not None:
                             segments.append((k, at, os.path.getsize(out_path)))
                 except BaseException as ex:
@@ -373,6 +394,10 @@ class FileTrimmer(object):
         self._tick('write_wait', t)
         if errors:
             raise errors[0]
+        if _bgzf_mode(self, out_format):
+            for path in [out_path] + [p for p, _ in bins.values()]:
+                if os.path.isfile(path):
+                    misc.bgzf_finish(path)
         return counts
 
     def _write_bins(self, b, out_format, st, et, co, cu, keep, calls, bins, k=0, segments=None):
@@ -393,7 +418,8 @@ class FileTrimmer(object):
             at = 0 if fresh else os.path.getsize(path)
             emitted = misc.write_reads(b, path, out_format, st, et, None, self.min_split, self.discard_middle,
                                        untrimmed=self.untrimmed, select=mask, append=not fresh, cut_arrays=(co, cu),
-                                       gzip_device=getattr(self, 'gzip_device', None))
+                                       gzip_device=getattr(self, 'gzip_device', None),
+                                         bgzf=_bgzf_mode(self, out_format))
             if emitted == 0:
                 if fresh and os.path.exists(path):
                     os.remove(path)             # the reference never opens an empty bin

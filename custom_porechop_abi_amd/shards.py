@@ -370,7 +370,7 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
                       check_reads=10000, adapter_threshold=90.0, max_reads=100000, group=None, device=None,
                       trimmer_factory=None, barcode_dir=None, barcode_threshold=75.0, barcode_diff=5.0,
                       require_two_barcodes=False, untrimmed=False, discard_unassigned=False, inflate_dir=None,
-                      spool_chunk_bytes=None, gzip_on_device=False):
+                      spool_chunk_bytes=None, gzip_on_device=False, bgzf=False):
     """The CLI's file-to-file path (porechop_abi.py:41-131: adapter-set search on the first
     check_reads records, end trim, middle scan, the fork's filter, trimmed output) on every rank of
     `group`, one GPU each:
@@ -402,6 +402,8 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
     import os
     import shutil
     from . import misc
+    if bgzf:
+        raise ValueError('BGZF output is not available for sharded runs: use pipeline.FileTrimmer(bgzf=True)')
     dist = _dist()
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -637,6 +637,13 @@ typedef struct pcabi_reads_view {
     const int32_t *len;
 } pcabi_reads_view;
 int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out);
+/* pcabi_fastx_open for a block-gzipped (BGZF) file read through GPU `device`: the file is mapped and
+ * indexed at open (pcabi_gunzip_index); refills then come from groups of members inflated on a
+ * stream of the reader's own (the next group while the parser works on the current one) instead of
+ * zlib. A member that does not inflate is the reader's read error (PCABI_E_PARSE, "read error:
+ * ..."), raised after the records before it. A plain file, a gzip file that is not indexable and
+ * device < 0 behave exactly as pcabi_fastx_open. The calling thread's current device may change. */
+int pcabi_fastx_open_dev(const char *path, int raw, int device, pcabi_fastx **out);
 int pcabi_fastx_type(const pcabi_fastx *r);
 /* Byte-range reading of a plain (not gzip) file, for read shards split by position:
  *   pcabi_fastx_record_start : the first record start at or after `byte` (the file size if
@@ -677,7 +684,9 @@ void pcabi_io_release_cache(void);
  * calling thread's current device; pcabi_reads_write itself uses that for gz = 2). The records are
  * laid out exactly as for a plain file, cut into blocks by pcabi_gzip_plan_lines (PCABI_GZIP_LONG_LINE,
  * blocks up to 65535 bytes), compressed by pcabi_gzip_host and written or appended as gzip members:
- * the file decompresses to the bytes gz = 0 writes. gz = 0 / 1 behave as in pcabi_reads_write. */
+ * the file decompresses to the bytes gz = 0 writes. gz = 3: the same through pcabi_bgzf_host, one
+ * indexed BGZF member per block of at most 65280 bytes, without the end-of-file marker
+ * (pcabi_bgzf_write_eof finishes the file). gz = 0 / 1 behave as in pcabi_reads_write. */
 int pcabi_reads_write_dev(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
                           const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
                           const int64_t *cuts, int min_split_read_size, int discard_middle,
@@ -725,6 +734,73 @@ int64_t pcabi_gzip_host(int device, const uint8_t *in, int64_t n, const int64_t 
 int64_t pcabi_gzip_plan_lines(const char *text, int64_t n, int64_t long_line, int64_t cap, int64_t *block_off,
                               int64_t off_cap);
 void pcabi_gzip_last_times(double *copy_in, double *wait, double *copy_out);
+/* BGZF output from the same encoder (opt-in): one gzip member per block, each with the 18-byte BGZF
+ * header (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, "BC" 02 00, BSIZE = member bytes - 1), the
+ * block encoded exactly as above (its sync marker and the closing empty fixed block included),
+ * CRC-32 and ISIZE. Blocks hold 1..PCABI_BGZF_BLOCK_CAP (65280) bytes, so that a stored block with
+ * all overhead stays within 65536; block_off = NULL: fixed blocks of min(pcabi_gzip_block_len(),
+ * 65280); a longer block is refused like any bad list. Such a stream is indexable: bgzip -d,
+ * samtools, htslib and pcabi_gunzip_* read it member by member.
+ *   pcabi_bgzf_bound : capacity that always suffices (n_blocks = 0: fixed blocks).
+ *   pcabi_bgzf_host  : as pcabi_gzip_host; eof != 0 appends the standard 28-byte end-of-file member
+ *       (1f8b08040000000000ff0600424302001b0003000000000000000000). No bytes give no member.
+ *   pcabi_bgzf_write_eof : appends that marker to a file.
+ *   pcabi_reads_write_dev(..., gz = 3, ...) is the record writer in this mode (blocks planned with cap
+ *       65280); it never writes the marker, so appended batches stay one contiguous chain. */
+int64_t pcabi_bgzf_bound(int64_t n, int64_t n_blocks, int eof);
+int64_t pcabi_bgzf_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks, int eof,
+                        uint8_t *out, int64_t cap);
+int pcabi_bgzf_write_eof(const char *path);
+
+/* ---- gunzip on the device (csrc/pcabi_inflate.hip) --------------------------------------
+ * Block-gzipped input (BGZF, what bgzip / htslib write): a gzip stream whose every member carries
+ * its own compressed size in the header's BC extra subfield and decodes to at most 65536 bytes.
+ * The host lists the members without decoding a byte; the device inflates them, one workgroup per
+ * member: RFC 1951 in full (stored, fixed and dynamic blocks, LZ77 matches), ISIZE and CRC-32
+ * checked. One int32 status per member: 0, or a PCABI_INFLATE_E_* below.
+ *   pcabi_gunzip_index : (host) walks the members of z[0, n) by their headers (FEXTRA with any
+ *       number of subfields, of which BC with SLEN 2 gives BSIZE = member bytes - 1). Writes
+ *       in_off[0..m] (member starts, in_off[m] = n) and out_off[0..m] (prefix sums of ISIZE) when
+ *       m + 1 <= cap; returns m. Returns 0, nothing written, when the stream is not indexable (a
+ *       member without BC, with CM != 8 or with ISIZE > 65536): use zlib then. PCABI_E_PARSE when
+ *       a member does not start with the gzip magic or the chain runs past n (truncated file). The
+ *       empty 28-byte end-of-file member is an ordinary member with ISIZE 0, anywhere.
+ *   pcabi_gunzip_scratch_bytes : device scratch pcabi_gunzip_dev needs (0 today: the decode tables
+ *       live in LDS; scratch may then be NULL).
+ *   pcabi_gunzip_dev : device pointers on the current device, asynchronous on `stream`, no host
+ *       synchronisation. Member k = z[in_off[k], in_off[k + 1]) decodes into out[out_off[k],
+ *       out_off[k + 1]). A member whose status is non-zero leaves its output range undefined and
+ *       touches nothing outside it; a member whose ranges do not lie inside [0, n) / [0, out_cap)
+ *       (an out_cap too small, for one) gets PCABI_INFLATE_E_OUTPUT / _E_HEADER and writes
+ *       nothing. Returns 0 or a negative PCABI_E_* for bad arguments.
+ *   pcabi_gunzip_host : host buffers (pageable): indexes, then stages groups of members through
+ *       pinned chunks so copies and kernels overlap. Returns the decoded length; the needed length,
+ *       with out untouched, when cap is smaller; PCABI_E_PARSE when a member fails (the message
+ *       names the first failing member's index, offset and status); PCABI_E_ARG when the stream is
+ *       not indexable. device -1 = current device.
+ *   pcabi_gunzip_tune : test switch, process-wide: decoded bytes per staged pass of
+ *       pcabi_gunzip_host and per refill group of the reader (0 = the default, 32 MiB).
+ *   pcabi_gunzip_last_times : seconds the last pcabi_gunzip_host call spent copying into pinned
+ *       memory, waiting for the device, and copying out of pinned memory.
+ */
+enum { PCABI_BGZF_BLOCK_CAP = 65280, PCABI_BGZF_MEMBER_MAX = 65536 };
+enum {
+    PCABI_INFLATE_E_HEADER = 1,   /* bad gzip or block header                  */
+    PCABI_INFLATE_E_CODE = 2,     /* bad Huffman code or symbol                */
+    PCABI_INFLATE_E_DIST = 3,     /* distance before the member's first byte   */
+    PCABI_INFLATE_E_INPUT = 4,    /* ran out of input                          */
+    PCABI_INFLATE_E_OUTPUT = 5,   /* more output than ISIZE                    */
+    PCABI_INFLATE_E_LENGTH = 6,   /* less output than ISIZE                    */
+    PCABI_INFLATE_E_CRC = 7       /* CRC-32 mismatch                           */
+};
+int64_t pcabi_gunzip_index(const uint8_t *z, int64_t n, int64_t *in_off, int64_t *out_off, int64_t cap);
+int64_t pcabi_gunzip_scratch_bytes(int64_t n_members);
+int pcabi_gunzip_dev(void *stream, const uint8_t *z, int64_t n, const int64_t *in_off, const int64_t *out_off,
+                     int64_t n_members, uint8_t *out, int64_t out_cap, int32_t *status, void *scratch,
+                     int64_t scratch_len);
+int64_t pcabi_gunzip_host(int device, const uint8_t *z, int64_t n, uint8_t *out, int64_t cap);
+int pcabi_gunzip_tune(int64_t chunk_bytes);
+void pcabi_gunzip_last_times(double *copy_in, double *wait, double *copy_out);
 
 #ifdef __cplusplus
 }
