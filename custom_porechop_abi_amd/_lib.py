@@ -142,6 +142,10 @@ def lib():
         'pcabi_gunzip_host': ([c_int, c_p, c_i64, c_p, c_i64], c_i64),
         'pcabi_gunzip_tune': ([c_i64], c_int),
         'pcabi_gunzip_last_times': ([c_p, c_p, c_p], None),
+        'pcabi_bam_index': ([c_p, c_i64, c_p, c_i64, c_p], c_i64),
+        'pcabi_bam_unpack_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
+        'pcabi_bam_unpack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
+        'pcabi_bam_last_times': ([c_int, c_int, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -181,7 +185,8 @@ def exported_symbols():
             'pcabi_reads_write_last_times',
             'pcabi_gunzip_index', 'pcabi_gunzip_scratch_bytes', 'pcabi_gunzip_dev', 'pcabi_gunzip_host',
             'pcabi_gunzip_tune', 'pcabi_gunzip_last_times', 'pcabi_bgzf_bound', 'pcabi_bgzf_host',
-            'pcabi_bgzf_write_eof']
+            'pcabi_bgzf_write_eof', 'pcabi_bam_index', 'pcabi_bam_unpack_dev', 'pcabi_bam_unpack_host',
+            'pcabi_bam_last_times']
 
 
 class CrossRegion(ctypes.Structure):

@@ -27,6 +27,10 @@
 
 namespace pcabi_internal {
 int fail(int code, const std::string &msg);
+// device-event spans of the BAM timing tool (pcabi_bam.hip): no-ops unless profiling is on
+bool prof_on();
+void *prof_begin(void *stream, int kind);
+void prof_end(void *stream, void *span);
 }
 using pcabi_internal::fail;
 using namespace pcabi_inflate;
@@ -273,11 +277,16 @@ int gunzip_group_async(void *stream, const uint8_t *z, const int64_t *in_off, co
         pin_off[m - m0] = in_off[m] - lo;
         pin_off[nm + 1 + m - m0] = out_off[m] - olo;
     }
+    const bool prof = prof_on();
+    void *sp = prof ? prof_begin(st, 2) : nullptr;
     if (bytes > 0) GUZ_TRY(hipMemcpyAsync(dev_in, pin_in, (size_t)bytes, hipMemcpyHostToDevice, st));
     GUZ_TRY(hipMemcpyAsync(dev_off, pin_off, 16 * (size_t)(nm + 1), hipMemcpyHostToDevice, st));
+    if (prof) prof_end(st, sp), sp = prof_begin(st, 0);
     if (int rc = launch(st, dev_in, bytes, dev_off, dev_off + nm + 1, nm, dev_out, obytes, dev_status)) return rc;
+    if (prof) prof_end(st, sp), sp = prof_begin(st, 3);
     if (nm > 0) GUZ_TRY(hipMemcpyAsync(pin_status, dev_status, 4 * (size_t)nm, hipMemcpyDeviceToHost, st));
     if (obytes > 0) GUZ_TRY(hipMemcpyAsync(pin_out, dev_out, (size_t)obytes, hipMemcpyDeviceToHost, st));
+    if (prof) prof_end(st, sp);
     return 0;
 }
 
@@ -393,6 +402,40 @@ int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room) {
             if (int rc = reader_launch(g, p + 1)) return rc;
     }
 }
+
+// The rest of the current group, or the next group, in place: its bytes in pinned memory (*host) and
+// on the device (*dev), both valid until the call after the next one; *stream = the stream that
+// inflated it (the group two further on is launched on it). Returns the length (> 0), 0 at the end of
+// the stream, or a negative code as gunzip_reader_read does.
+int64_t gunzip_reader_take(GunzipReader *g, const uint8_t **host, const uint8_t **dev, void **stream) {
+    for (;;) {
+        if (g->cur_at < g->cur_len) {
+            Slot &s = g->s[(g->consume - 1) % kSlots];
+            const int64_t k = g->cur_len - g->cur_at;
+            *host = g->cur + g->cur_at;
+            *dev = s.dev_out + g->cur_at;
+            *stream = s.st;
+            g->cur_at = g->cur_len;
+            return k;
+        }
+        char none;
+        const int64_t rc = gunzip_reader_read(g, &none, 0);   // room 0: moves to the next group, copies nothing
+        if (rc < 0) return rc;
+        if (g->cur_at >= g->cur_len) {
+            if (g->pending) return fail(g->pending, g->pending_msg);
+            if (g->consume >= g->np) return 0;
+        }
+    }
+}
+
+// hand the current group out again from its first byte (the type sniff of pcabi_fastx_open_dev read
+// from it)
+void gunzip_reader_unread(GunzipReader *g) { g->cur_at = 0; }
+
+int gunzip_reader_device(const GunzipReader *g) { return g->device; }
+
+// the stream's decoded length, from the index
+int64_t gunzip_reader_total(const GunzipReader *g) { return g->out_off.empty() ? 0 : g->out_off.back(); }
 
 void gunzip_reader_close(GunzipReader *g) {
     if (g) reader_free(g);

@@ -6,7 +6,9 @@
 // read names, upper-cased sequence text and qualities, in batches, with the reference's parsing
 // rules:
 //   * file type from the first decoded character: '>' FASTA, '@' FASTQ, else an error
-//     (porechop_abi/misc.py:84-105); gzip by its magic bytes, bzip2 / zip refused (:60-81);
+//     (porechop_abi/misc.py:84-105); gzip by its magic bytes, bzip2 / zip refused (:60-81); a file
+//     whose first decoded bytes are "BAM" is an unaligned BAM file: its records (pcabi_bam.h) become
+//     a FASTQ batch, unpacked on the device when the reader inflates there (BamState below);
 //   * FASTQ: 4 lines per record, each stripped; name = line[1:] (the full header), sequence,
 //     spacer, qualities (misc.py:148-165); a blank or truncated record is a parse error (the
 //     reference dies on it too);
@@ -51,6 +53,7 @@
 #include <vector>
 
 #include "../../include/pcabi.h"
+#include "pcabi_bam.h"
 #include "pcabi_deflate.h"
 
 namespace pcabi_internal {
@@ -84,7 +87,40 @@ struct GunzipReader;
 int gunzip_reader_open(const uint8_t *z, int64_t n, int device, GunzipReader **out);
 int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room);
 void gunzip_reader_close(GunzipReader *g);
+int64_t gunzip_reader_take(GunzipReader *g, const uint8_t **host, const uint8_t **dev, void **stream);
+void gunzip_reader_unread(GunzipReader *g);
+int gunzip_reader_device(const GunzipReader *g);
+int64_t gunzip_reader_total(const GunzipReader *g);
+// the device half of a BAM reader (csrc/pcabi_bam.hip)
+struct BamDev;
+int bam_dev_open(int device, BamDev **out);
+void bam_dev_close(BamDev *b);
+int bam_dev_append(BamDev *b, int64_t keep_from, const uint8_t *src, int64_t n, void *stream);
+int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const pcabi_bam::Layout &lay,
+                   const uint8_t **seq, const uint8_t **qual, const uint8_t **codes);
 }  // namespace pcabi_internal
+
+// A BAM input's state. win[0, end) is a window of the inflated bytes (on the device path mirrored there,
+// pcabi_bam.hip BamDev): the record chain is walked from `at`, whole records are unpacked into the
+// stage -- a table, their names and their sequence / quality / code bytes in the batch layout, whose
+// code offsets are multiples of four, so any run of staged records is appended to a batch by plain
+// copies -- and the incomplete record at the window's end is carried in front of the next bytes.
+struct BamState {
+    std::vector<uint8_t> win;
+    size_t at = 0, end = 0;
+    int64_t base = 0;                 // the stream offset of win[0] (error messages)
+    int64_t total_est = 0;            // the stream's inflated length (the index's sum), or a guess from the file size
+    bool header_done = false, eof = false;
+    int pending = 0;                  // a fault: raised once the records before it are delivered
+    std::string pending_msg;
+    std::vector<pcabi_bam_rec> recs;  // the stage; [next, size) not yet delivered
+    size_t next = 0;
+    std::vector<char> names;
+    std::vector<int64_t> name_off;
+    std::vector<uint8_t> h_seq, h_qual, h_codes;   // the host path's outputs
+    const uint8_t *seq = nullptr, *qual = nullptr, *codes = nullptr;
+    pcabi_internal::BamDev *dev = nullptr;
+};
 
 struct pcabi_fastx {
     gzFile f = nullptr;
@@ -92,6 +128,7 @@ struct pcabi_fastx {
     void *zmap = nullptr;                          // its compressed bytes, mapped whole
     size_t zmap_len = 0;
     int type = -1;                 // PCABI_FASTA / PCABI_FASTQ
+    BamState *bam = nullptr;       // the input is a BAM file (type PCABI_FASTQ): records instead of lines
     std::vector<char> buf;         // gzip: decoded bytes [0, end)
     const char *base = nullptr;    // buf.data(), or the mapping of a plain file
     void *map = nullptr;           // plain files are memory-mapped whole
@@ -638,7 +675,26 @@ static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **
         }
     }
     const char c0 = r->end ? r->base[0] : 0;
-    if (c0 == '>') r->type = PCABI_FASTA;
+    if (!r->map && r->end >= 4 && std::memcmp(r->base, "BAM", 3) == 0) {
+        // unaligned BAM: the version byte is checked with the header (a read error of the first batch)
+        r->type = PCABI_FASTQ;
+        r->bam = new BamState();
+        r->bam->total_est = r->dev ? pcabi_internal::gunzip_reader_total(r->dev) : (int64_t)r->size_hint;
+        if (r->dev) {
+            pcabi_internal::gunzip_reader_unread(r->dev);   // the first group again, in place
+            if (int rc = pcabi_internal::bam_dev_open(pcabi_internal::gunzip_reader_device(r->dev), &r->bam->dev)) {
+                pcabi_fastx_close(r);
+                return rc;
+            }
+        } else {
+            r->bam->win.assign((const uint8_t *)r->base, (const uint8_t *)r->base + r->end);
+            r->bam->end = r->end;
+            r->bam->eof = r->eof;
+        }
+        r->pos = r->end = 0;
+        std::vector<char>().swap(r->buf);
+        r->base = nullptr;
+    } else if (c0 == '>') r->type = PCABI_FASTA;
     else if (c0 == '@') r->type = PCABI_FASTQ;
     else {
         pcabi_fastx_close(r);
@@ -738,6 +794,10 @@ int pcabi_fastx_set_range(pcabi_fastx *r, int64_t begin, int64_t end) {
 void pcabi_fastx_close(pcabi_fastx *r) {
     if (!r) return;
     if (r->f) gzclose(r->f);
+    if (r->bam) {
+        pcabi_internal::bam_dev_close(r->bam->dev);   // before the streams it used go
+        delete r->bam;
+    }
     if (r->dev) pcabi_internal::gunzip_reader_close(r->dev);
     if (r->zmap) munmap(r->zmap, r->zmap_len);
     r->ahead_stop = true;                 // the populate-ahead helper leaves the mapping first
@@ -751,8 +811,11 @@ void pcabi_fastx_close(pcabi_fastx *r) {
     delete r;
 }
 
+static int64_t bam_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, pcabi_reads **out);
+
 int64_t pcabi_fastx_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, pcabi_reads **out) {
     if (!r || !out || max_reads <= 0) return fail(PCABI_E_ARG, "bad arguments");
+    if (r->bam) return bam_next(r, max_reads, max_bases, out);
     if (r->map && !r->ahead.joinable() && r->end > r->pos + (64u << 20)) {
         // a large plain file read in batches: the helper maps pages ahead of the record scan
         r->reader_at.store(r->pos, std::memory_order_relaxed);
@@ -876,6 +939,7 @@ int64_t pcabi_fastx_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, p
 // (one record may overshoot). *text stays valid until the next call on r. Returns 1, 0 at the end.
 int pcabi_fastx_next_text(pcabi_fastx *r, int64_t max_bytes, const char **text, int64_t *len) {
     if (!r || !text || !len || max_bytes <= 0) return fail(PCABI_E_ARG, "bad arguments");
+    if (r->bam) return fail(PCABI_E_ARG, "text spans are not available for a BAM input (its records are binary)");
     r->pin = r->pos;
     const char *p;
     size_t n;
@@ -908,13 +972,224 @@ int pcabi_fastx_next_text(pcabi_fastx *r, int64_t max_bytes, const char **text, 
     return *len > 0 ? 1 : 0;
 }
 
+// ---- BAM records -----------------------------------------------------------------------------
+// More inflated bytes behind the carried ones: > 0, 0 at the end of the stream (or at a read error, which
+// becomes the pending fault), a negative code for a device error.
+static int64_t bam_refill(pcabi_fastx *r) {
+    BamState *s = r->bam;
+    const size_t carry = s->end - s->at;
+    const int64_t keep_from = (int64_t)s->at;
+    if (s->at > 0) {
+        std::memmove(s->win.data(), s->win.data() + s->at, carry);
+        s->base += (int64_t)s->at;
+        s->at = 0;
+        s->end = carry;
+    }
+    int64_t got;
+    std::string msg;
+    if (r->dev) {
+        const uint8_t *host = nullptr, *dev = nullptr;
+        void *stream = nullptr;
+        got = pcabi_internal::gunzip_reader_take(r->dev, &host, &dev, &stream);
+        if (got < 0 && got != PCABI_E_PARSE) return got;
+        if (got < 0) msg = pcabi_last_error();
+        if (got > 0) {
+            // (at the end of the stream nothing whole is left to unpack: the mirror may keep its old offsets)
+            if (int rc = pcabi_internal::bam_dev_append(s->dev, keep_from, dev, got, stream)) return rc;
+            if (s->win.size() < s->end + (size_t)got) s->win.resize(s->end + (size_t)got);
+            std::memcpy(s->win.data() + s->end, host, (size_t)got);
+        }
+    } else {
+        constexpr size_t kRead = 4u << 20;
+        if (s->win.size() < s->end + kRead) s->win.resize(s->end + kRead);
+        got = gzread(r->f, s->win.data() + s->end, (unsigned)kRead);
+        int zerr = Z_OK;
+        const char *zmsg = got <= 0 ? gzerror(r->f, &zerr) : nullptr;
+        if (got < 0 || (got == 0 && zerr != Z_OK && zerr != Z_STREAM_END)) {
+            msg = zmsg ? zmsg : "?";
+            got = -1;
+        }
+    }
+    if (got < 0) {
+        s->pending = PCABI_E_PARSE;
+        s->pending_msg = "read error: " + msg;
+        s->eof = true;
+        return 0;
+    }
+    if (got == 0) s->eof = true;
+    s->end += (size_t)got;
+    return got;
+}
+
+static void bam_fault(BamState *s, const std::string &what) {
+    if (s->pending) return;
+    s->pending = PCABI_E_PARSE;
+    s->pending_msg = "read error: " + what;
+    s->eof = true;
+}
+
+// Fills the empty stage with the next whole records. Leaves it empty at the end of the input or at a
+// fault (s->pending). Returns 0, or a negative code for a device error.
+static int bam_fill(pcabi_fastx *r) {
+    using namespace pcabi_bam;
+    BamState *s = r->bam;
+    s->recs.clear();
+    s->names.clear();
+    s->name_off.assign(1, 0);
+    s->next = 0;
+    Layout lay;
+    while (s->recs.empty() && !s->pending) {
+        // what the window holds: the header, then whole records from `at`
+        if (!s->header_done) {
+            const int64_t h = header_len(s->win.data(), (int64_t)s->end);
+            if (h < 0) {
+                bam_fault(s, s->end >= 4 && s->win[3] != 1 ? "BAM version byte " + std::to_string((int)s->win[3]) + " is not supported"
+                                                           : std::string("invalid BAM header"));
+                break;
+            }
+            if (h > 0) {
+                s->header_done = true;
+                s->at = (size_t)h;
+            }
+        }
+        if (s->header_done) {
+            int64_t at = (int64_t)s->at;
+            bool invalid = false;
+            for (;;) {
+                pcabi_bam_rec rec;
+                int64_t size = 0;
+                const int rc = record_at(s->win.data(), (int64_t)s->end, at, &rec, &size);
+                if (rc <= 0) {
+                    invalid = rc < 0;
+                    break;
+                }
+                at += size;
+                if (rec.flag & kSkipFlags) continue;
+                lay.place(&rec);
+                s->recs.push_back(rec);
+                const char *nm = (const char *)s->win.data() + rec.rec + 4 + kFixed;
+                s->names.insert(s->names.end(), nm, nm + rec.name_len);
+                s->name_off.push_back((int64_t)s->names.size());
+            }
+            s->at = (size_t)at;
+            if (invalid) bam_fault(s, "invalid BAM record at offset " + std::to_string(s->base + at));
+        }
+        if (!s->recs.empty() || s->pending) break;
+        // nothing whole in the window: more bytes behind the carried ones, or the end
+        if (r->dev && s->header_done && s->end - s->at >= 4) {
+            // the index knows the stream's length: a record that runs past it fails now, not after the
+            // rest of the file has been carried into the window
+            const int64_t block = le32(s->win.data() + s->at), rec_at = s->base + (int64_t)s->at;
+            if (rec_at + 4 + block > s->total_est) {
+                bam_fault(s, "truncated BAM record at offset " + std::to_string(rec_at));
+                break;
+            }
+        }
+        if (s->eof) {
+            if (!s->header_done) bam_fault(s, "truncated BAM header");
+            else if (s->at < s->end) bam_fault(s, "truncated BAM record at offset " + std::to_string(s->base + (int64_t)s->at));
+            break;
+        }
+        const int64_t got = bam_refill(r);
+        if (got < 0) return (int)got;
+    }
+    if (!s->recs.empty()) {
+        if (s->dev) {
+            if (int rc = pcabi_internal::bam_dev_unpack(s->dev, s->recs.data(), (int64_t)s->recs.size(), lay, &s->seq, &s->qual,
+                                                        &s->codes))
+                return rc;
+        } else {
+            s->h_seq.resize((size_t)lay.seq);
+            s->h_qual.resize((size_t)lay.seq);
+            s->h_codes.resize((size_t)lay.code);
+            for (const pcabi_bam_rec &q : s->recs)
+                unpack_range(s->win.data() + q.rec + q.seq_at, q.l_seq, q.flag, 0, q.l_seq, s->h_seq.data() + q.seq_out,
+                             s->h_qual.data() + q.qual_out, s->h_codes.data() + q.code_out);
+            s->seq = s->h_seq.data();
+            s->qual = s->h_qual.data();
+            s->codes = s->h_codes.data();
+        }
+    }
+    return 0;
+}
+
+static int64_t bam_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, pcabi_reads **out) {
+    BamState *s = r->bam;
+    pcabi_reads *b = new pcabi_reads();
+    b->type = PCABI_FASTQ;
+    int64_t bases = 0;
+    while (b->n < max_reads && bases < max_bases) {
+        if (s->next >= s->recs.size()) {
+            if (int rc = bam_fill(r)) {
+                delete b;
+                return rc;
+            }
+            if (s->recs.empty()) break;   // the end of the input, or a fault
+        }
+        const size_t i = s->next;
+        size_t j = i;
+        while (j < s->recs.size() && b->n + (int64_t)(j - i) < max_reads && bases < max_bases) bases += s->recs[j++].l_seq;
+        const pcabi_bam_rec &first = s->recs[i], &last = s->recs[j - 1];
+        if (b->n == 0) {
+            // room for the batch at once when it is large (growing gigabyte buffers by doubling copies
+            // them twice over): the bases max_bases allows, but no more than the staged records and the
+            // input behind the window can hold (a base takes a byte and a half of a record). A batch
+            // that outgrows it grows as any vector does.
+            const pcabi_bam_rec &end = s->recs.back();
+            const int64_t staged = end.seq_out + end.l_seq - first.seq_out;
+            const int64_t behind = std::max<int64_t>(0, s->total_est - s->base - (int64_t)s->end);
+            const int64_t want = std::min(max_bases, staged + behind / 3 * 2);
+            if (want >= (int64_t)bigmem::kBig) {   // smaller buffers come from malloc and grow cheaply
+                b->seq.reserve((size_t)want);
+                b->qual.reserve((size_t)want);
+                b->codes.reserve((size_t)want + (size_t)want / 8);   // padding: at most 3 bytes a read
+            }
+        }
+        const int64_t c0 = first.code_out, c1 = last.code_out + (((int64_t)last.l_seq + 3) & ~(int64_t)3);
+        const int64_t code_base = (int64_t)b->codes.size();
+        b->seq.insert(b->seq.end(), s->seq + first.seq_out, s->seq + last.seq_out + last.l_seq);
+        b->qual.insert(b->qual.end(), s->qual + first.qual_out, s->qual + last.qual_out + last.l_seq);
+        b->codes.insert(b->codes.end(), s->codes + c0, s->codes + c1);
+        b->names.insert(b->names.end(), s->names.data() + s->name_off[i], s->names.data() + s->name_off[j]);
+        for (size_t k = i; k < j; ++k) {
+            const pcabi_bam_rec &q = s->recs[k];
+            b->name_off.push_back(b->name_off.back() + (s->name_off[k + 1] - s->name_off[k]));
+            b->seq_off.push_back(b->seq_off.back() + q.l_seq);
+            b->qual_off.push_back(b->qual_off.back() + q.l_seq);
+            b->spacer_off.push_back(0);
+            b->rna.push_back(0);
+            b->code_off.push_back(code_base + (q.code_out - c0));
+            b->len.push_back(q.l_seq);
+        }
+        b->n += (int64_t)(j - i);
+        s->next = j;
+    }
+    if (b->n == 0 && s->pending) {
+        delete b;
+        return fail(s->pending, s->pending_msg);
+    }
+    finish_batch(b);
+    *out = b;
+    return b->n;
+}
+
 int pcabi_fastx_load(const char *path, int raw, pcabi_reads **out) {
     if (!out) return fail(PCABI_E_ARG, "bad arguments");
     *out = nullptr;
     pcabi_fastx *r = nullptr;
     if (int rc = pcabi_fastx_open(path, raw, &r)) return rc;
     pcabi_reads *all = nullptr;
-    const int64_t got = pcabi_fastx_next(r, INT64_MAX, INT64_MAX, &all);
+    int64_t got = pcabi_fastx_next(r, INT64_MAX, INT64_MAX, &all);
+    if (got >= 0 && r->bam) {
+        // a BAM reader delivers the records before a fault first: the fault is the next call's
+        pcabi_reads *none = nullptr;
+        const int64_t more = pcabi_fastx_next(r, 1, 1, &none);
+        delete none;
+        if (more < 0) {
+            delete all;
+            got = more;
+        }
+    }
     pcabi_fastx_close(r);
     if (got < 0) return (int)got;
     *out = all;

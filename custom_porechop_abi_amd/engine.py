@@ -744,3 +744,51 @@ def gunzip(data, device=0, cap=None):
     if n > size:
         raise ValueError('gunzip: capacity %d, needed %d' % (size, n))
     return out[:n].tobytes()
+
+
+# ---- unaligned BAM input (csrc/pcabi_bam.h, csrc/pcabi_bam.hip) ----------------------------------
+# include/pcabi.h pcabi_bam_rec
+BAM_REC = np.dtype([('rec', np.int64), ('seq_out', np.int64), ('qual_out', np.int64), ('code_out', np.int64),
+                    ('tile0', np.int64), ('seq_at', np.int32), ('l_seq', np.int32), ('flag', np.int32),
+                    ('name_len', np.int32)])
+
+
+def bam_index(data):
+    """The records of a whole inflated BAM file (pcabi_bam_index): (recs, totals). recs: a BAM_REC
+    array of the kept records (secondary and supplementary ones skipped) with their output offsets
+    in the batch layout; totals: int64 [5] = sequence bytes, quality bytes, code bytes (16 bytes of
+    tail padding included), name bytes, tiles. A bad header, an invalid record or a truncated chain
+    raises PcabiError."""
+    buf, _ = _gzip_input(data, None)
+    L = lib()
+    totals = np.zeros(5, np.int64)
+    n = L.pcabi_bam_index(_ptr(buf), buf.size, None, 0, _ptr(totals))
+    if n < 0:
+        check(int(n), 'pcabi_bam_index')
+    recs = np.zeros(int(n), BAM_REC)
+    if n > 0:
+        L.pcabi_bam_index(_ptr(buf), buf.size, _ptr(recs), int(n), _ptr(totals))
+    return recs, totals
+
+
+def bam_unpack(data, recs, totals=None, device=0, out=None):
+    """The records of a bam_index table unpacked from the inflated bytes `data` into (seq, qual,
+    codes) uint8 arrays in the batch layout (pcabi_bam_unpack_host): on GPU `device`, or with the
+    host build of the same code when device < 0. out: three preallocated C-contiguous uint8 arrays
+    to fill instead (bytes no record owns keep their values); totals: bam_index's, for the sizes and
+    the place of the 16 bytes of tail padding."""
+    buf, _ = _gzip_input(data, None)
+    recs = np.ascontiguousarray(recs, BAM_REC)
+    if totals is None:
+        ln = recs['l_seq'].astype(np.int64)
+        totals = np.array([ln.sum(), ln.sum(), ((ln + 3) & ~3).sum() + 16, 0, 0], np.int64)
+    if out is None:
+        out = (np.zeros(int(totals[0]), np.uint8), np.zeros(int(totals[1]), np.uint8), np.zeros(int(totals[2]), np.uint8))
+    seq, qual, codes = out
+    for a in out:
+        if a.dtype != np.uint8 or not a.flags['C_CONTIGUOUS']:
+            raise ValueError('bam_unpack: outputs are C-contiguous uint8 arrays')
+    rc = lib().pcabi_bam_unpack_host(int(device), _ptr(buf), buf.size, _ptr(recs), recs.size, _ptr(seq), seq.size,
+                                     _ptr(qual), qual.size, _ptr(codes), codes.size, int(totals[2]) - 16)
+    check(int(rc), 'pcabi_bam_unpack_host')
+    return seq, qual, codes

@@ -164,9 +164,9 @@ def _open_error(path):
 
 
 def input_files(path):
-    """The sequence files of an input, as load_reads sees it (porechop_abi.py:133-187): a file is
-    itself (albacore barcode None); a directory is an Albacore output directory -- every *.fastq /
-    *.fastq.gz under it, sorted by path, each with the barcode its path names
+    """The sequence files of an input, as load_reads sees it (porechop_abi.py:133-187): a file (FASTA,
+    FASTQ or BAM, plain or gzip) is itself (albacore barcode None); a directory is an Albacore output
+    directory -- every *.fastq / *.fastq.gz under it, sorted by path, each with the barcode its path names
     (get_albacore_barcode_from_path). Exits like the reference when nothing is found."""
     if os.path.isfile(path):
         return [(path, None)]
@@ -243,6 +243,19 @@ def _starts_bgzf(path):
     return False
 
 
+def is_bam(path):
+    """Whether the file is a BAM file: gzip (BGZF) whose decoded bytes start with 'BAM'."""
+    import zlib
+    try:
+        with open(path, 'rb') as f:
+            head = f.read(1 << 16)
+        if head[:3] != b'\x1f\x8b\x08':
+            return False
+        return zlib.decompressobj(31).decompress(head, 4)[:3] == b'BAM'
+    except (OSError, zlib.error):
+        return False
+
+
 def _fastx_open(L, path, raw, gunzip_device):
     """pcabi_fastx_open, or pcabi_fastx_open_dev when gunzip_device names a GPU (a block-gzipped file
     is then inflated there; any other file reads as before). Returns (rc, handle)."""
@@ -267,13 +280,15 @@ def ramp_sizes(max_reads, remaining_reads=None, done=0):
 
 def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_range=None, first_reads=None,
                  ramp=False, gunzip_device=None):
-    """Stream a FASTA / FASTQ(.gz) file as ReadBatch objects (pcabi_fastx_next); byte_range =
+    """Stream a FASTA / FASTQ(.gz) or unaligned BAM file as ReadBatch objects (pcabi_fastx_next; a BAM
+    file's records arrive as FASTQ batches, see include/pcabi.h "unaligned BAM input"); byte_range =
     (begin, end) record starts of a plain file (record_boundaries) reads only that range;
     first_reads: the first batch's size, if other than max_reads (a pipeline starts its later
     stages sooner on a small first batch); ramp: batch sizes from ramp_sizes (a plain file's last
     batches shrink too, from the bytes left and the bytes per read so far). Batching never changes
     what is read or written, only when. gunzip_device: a GPU that inflates a block-gzipped (BGZF)
-    input (pcabi_fastx_open_dev); None reads every gzip input with zlib."""
+    input (pcabi_fastx_open_dev) and, for a BAM file, unpacks its records; None reads every gzip
+    input with zlib."""
     L = _declare(lib())
     rc, h = _fastx_open(L, path, raw, gunzip_device)
     if rc != 0:
@@ -309,7 +324,8 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
 
 
 def text_chunks(path, chunk_bytes, gunzip_device=None):
-    """Stream a FASTA / FASTQ(.gz) file as spans of its decoded text holding whole records, cut
+    """Stream a FASTA / FASTQ(.gz) file (not BAM: its records are binary, the reader refuses) as
+    spans of its decoded text holding whole records, cut
     where a fresh reader parses the same records (pcabi_fastx_next_text): yields memoryviews of at
     least chunk_bytes (the last may be shorter), each valid until the next one is requested.
     gunzip_device: as in read_batches."""
@@ -331,8 +347,9 @@ def text_chunks(path, chunk_bytes, gunzip_device=None):
 
 
 def load_batch(path, raw=False, gunzip_device=None):
-    """The whole file as one ReadBatch (pcabi_fastx_load); raw keeps the file's own text.
-    gunzip_device: a GPU that inflates a block-gzipped (BGZF) input (pcabi_fastx_open_dev)."""
+    """The whole FASTA, FASTQ or BAM file as one ReadBatch (pcabi_fastx_load); raw keeps the file's
+    own text. gunzip_device: a GPU that inflates a block-gzipped (BGZF) input, a BAM file included,
+    whose records are then unpacked there too (pcabi_fastx_open_dev)."""
     L = _declare(lib())
     b = ctypes.c_void_p()
     if gunzip_device is not None and _starts_bgzf(path):
@@ -341,6 +358,15 @@ def load_batch(path, raw=False, gunzip_device=None):
             raise ValueError(_open_error(path))
         try:
             if L.pcabi_fastx_next(h, (1 << 63) - 1, (1 << 63) - 1, ctypes.byref(b)) < 0:
+                raise ValueError(_open_error(path))
+            # one more call, whatever the type: a BAM reader delivers the records before a fault first
+            # and raises on the next call; a FASTA / FASTQ reader returns no records here
+            more = ctypes.c_void_p()
+            rc = L.pcabi_fastx_next(h, 1, 1, ctypes.byref(more))
+            if rc >= 0:
+                L.pcabi_reads_free(more)
+            else:
+                L.pcabi_reads_free(b)
                 raise ValueError(_open_error(path))
         finally:
             L.pcabi_fastx_close(h)
@@ -367,7 +393,8 @@ def get_compression_type(filename):
 
 def load_fasta_or_fastq(filename):
     """misc.py:108-120 through the native reader in raw mode (the file's own text; the reference
-    normalises it later, in NanoporeRead)."""
+    normalises it later, in NanoporeRead). FASTA, FASTQ or BAM: a BAM file gives the 'FASTQ' tuples
+    (empty spacer line)."""
     if not os.path.isfile(filename):
         sys.exit('Error: could not find ' + filename)
     get_compression_type(filename)
@@ -412,7 +439,8 @@ def add_line_breaks_to_sequence(sequence, line_length):
 
 
 def load_reads(input_file_or_directory, verbosity, print_dest, check_read_count):
-    """porechop_abi.py:133-187: NanoporeRead objects from a file, or from every *.fastq(.gz)
+    """porechop_abi.py:133-187: NanoporeRead objects from a FASTA, FASTQ or BAM file, or from every
+    *.fastq(.gz)
     under an Albacore-style directory (check reads spread over the files, barcode from the path)."""
     if os.path.isfile(input_file_or_directory):
         if verbosity > 0:

@@ -404,6 +404,8 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
     from . import misc
     if bgzf:
         raise ValueError('BGZF output is not available for sharded runs: use pipeline.FileTrimmer(bgzf=True)')
+    if os.path.isfile(in_path) and misc.is_bam(in_path):
+        raise ValueError('BAM input is not available for sharded runs: use pipeline.FileTrimmer.trim_file')
     dist = _dist()
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -593,8 +593,9 @@ int pcabi_kmer_approx_host(int device, const uint8_t *codes, int64_t codes_len, 
  * Sequence files (host code, csrc/pcabi_io.cpp; replaces porechop_abi/misc.py:60-168
  * load_fasta_or_fastq and NanoporeRead's normalisation, nanopore_read.py:31-44, for the batched
  * path, and NanoporeRead.get_fasta / get_fastq, nanopore_read.py:84-156, for output).
- *   pcabi_fastx_open / next / close : streaming reader, plain or gzip, FASTA or FASTQ (by the
- *       first character), the reference's parse rules; next() returns up to max_reads records
+ *   pcabi_fastx_open / next / close : streaming reader, plain or gzip, FASTA, FASTQ (by the
+ *       first character) or unaligned BAM (first bytes "BAM"; see "unaligned BAM input" below),
+ *       the reference's parse rules; next() returns up to max_reads records
  *       (stopping once max_bases sequence bytes are in the batch) as a new pcabi_reads, or a
  *       negative PCABI_E_* (PCABI_E_PARSE for a malformed file); 0 records at end of file.
  *   pcabi_fastx_load : the whole file as one batch.
@@ -801,6 +802,59 @@ int pcabi_gunzip_dev(void *stream, const uint8_t *z, int64_t n, const int64_t *i
 int64_t pcabi_gunzip_host(int device, const uint8_t *z, int64_t n, uint8_t *out, int64_t cap);
 int pcabi_gunzip_tune(int64_t chunk_bytes);
 void pcabi_gunzip_last_times(double *copy_in, double *wait, double *copy_out);
+
+/* ---- unaligned BAM input (csrc/pcabi_bam.h, csrc/pcabi_bam.hip) ------------------------------
+ * The reader (pcabi_fastx_open / pcabi_fastx_open_dev) takes a BAM file as a third input type: its
+ * first four decoded bytes are "BAM\1". Batches are PCABI_FASTQ batches: name = read name, sequence
+ * letters over "=ACMGRSVTWYHKDBN", qualities q + 33 ('+' for every base when they are absent), rna 0,
+ * empty spacer; secondary (0x100) and supplementary (0x800) records are skipped, reverse-strand
+ * records (0x10) are reverse-complemented, tags are dropped. pcabi_fastx_open_dev unpacks the
+ * records on the device next to the inflated bytes. pcabi_fastx_remaining returns -1;
+ * pcabi_fastx_set_range, pcabi_fastx_record_start and pcabi_fastx_next_text refuse a BAM reader
+ * (PCABI_E_ARG). An invalid record, a truncated record chain, a member that does not inflate or
+ * "BAM" with another version byte is PCABI_E_PARSE ("read error: ..."), raised by the call after
+ * the one that delivered the records before the fault.
+ *   pcabi_bam_index : (host) bam[0, n) is a whole inflated BAM file. Skips the header, walks the
+ *       record chain and writes the kept records to recs[0, cap) with their output offsets in the
+ *       batch layout (sequence and qualities back to back, codes at 4-aligned starts). totals[0..4]
+ *       (may be NULL) = sequence bytes, quality bytes, code bytes (16 bytes of tail padding
+ *       included), name bytes, tiles. Returns the number of kept records (write again with a larger
+ *       cap when it exceeds cap) or PCABI_E_PARSE.
+ *   pcabi_bam_unpack_dev : device pointers on the current device, asynchronous on `stream`: the
+ *       records of recs[0, n_recs) (a table pcabi_bam_index made, tile0 ascending) from bam[0, n)
+ *       into seq / qual / codes. Every record writes its own ranges only: l_seq bytes of seq and
+ *       qual, l_seq rounded up to four bytes of codes (padding = 4); codes[tail_off, tail_off + 16)
+ *       is filled with 4 when tail_off >= 0. A record that does not lie inside the buffers writes
+ *       nothing. Returns 0 or PCABI_E_ARG.
+ *   pcabi_bam_unpack_host : the same with host buffers, staged through the device; device < 0 runs
+ *       the host build of the same code (no GPU needed). Table entries outside the buffers are
+ *       refused (PCABI_E_ARG). On the device every output starts as far off a 16-byte boundary as
+ *       the caller's pointer and lies between 64 guard bytes, which are checked after the kernel
+ *       (PCABI_E_DEVICE if it wrote outside an output).
+ *   pcabi_bam_last_times : milliseconds the device reader spent, from device events, since the last
+ *       call with reset != 0: ms[0] k_inflate, ms[1] k_bam_unpack, ms[2] copies to the device,
+ *       ms[3] copies from the device; bytes[0] = bytes k_bam_unpack read and wrote. Events are only
+ *       recorded while profiling is on (on = 1; on = 0 turns it off; -1 leaves it).
+ */
+typedef struct pcabi_bam_rec {
+    int64_t rec;        /* the record's start (its block_size field) in the inflated bytes   */
+    int64_t seq_out;    /* output offsets of base 0: sequence, qualities, codes              */
+    int64_t qual_out;
+    int64_t code_out;
+    int64_t tile0;      /* tiles of the records before this one (16384 bases per tile)        */
+    int32_t seq_at;     /* the packed sequence's offset from rec; the qualities follow it    */
+    int32_t l_seq;
+    int32_t flag;
+    int32_t name_len;   /* the name is at rec + 36                                           */
+} pcabi_bam_rec;
+int64_t pcabi_bam_index(const uint8_t *bam, int64_t n, pcabi_bam_rec *recs, int64_t cap, int64_t *totals);
+int pcabi_bam_unpack_dev(void *stream, const uint8_t *bam, int64_t n, const pcabi_bam_rec *recs, int64_t n_recs,
+                         int64_t n_tiles, uint8_t *seq, int64_t seq_cap, uint8_t *qual, int64_t qual_cap,
+                         uint8_t *codes, int64_t codes_cap, int64_t tail_off);
+int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi_bam_rec *recs, int64_t n_recs,
+                          uint8_t *seq, int64_t seq_cap, uint8_t *qual, int64_t qual_cap, uint8_t *codes,
+                          int64_t codes_cap, int64_t tail_off);
+void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
 
 #ifdef __cplusplus
 }
