@@ -1007,9 +1007,49 @@ struct LayT {
         return attr_start(c) | (nd << ATTR_B) | m;
     }
 };
+// Gap-extend frame of the run-tagged buckets (LaneShift below: cross-mode launches). Every key of
+// slot s (1..RPL, padding slots included) at column phase jj (columns since the last rebase) holds
+// its LayT value with the score moved by
+//      f(s, jj) = |ge| (s + jj) - B
+// so a horizontal step (jj + 1) and a vertical step (s + 1) both add |ge| to the frame: a gap EXTEND
+// leaves the key as it is, and the cell loses LayT's two extend adds. A gap open costs OPEN = go -
+// ge in the frame, a diagonal step sub - 2 ge (folded into the substitution keys, sub_key_shift).
+// All comparands of one max are keys of the same (s, jj), so every max compares the LayT scores.
+// Fields as LayT: [ score : 8 ][ tag : 7 ][ c mod 128 : 7 ][ nD : 5 ][ m : 5 ].
+//
+// Tags. An extend no longer touches the key, so a tag cannot count extends; instead an open takes
+// a tag that FALLS with the column (H) or the row (V), and the older run -- the extend -- still
+// wins a tie. With A(jj) = P - 1 - jj (P: the rebase period), at phase jj:
+//   stored G(s) (= S with the tag cleared + OPEN)       tag A(jj)
+//   H: open = G of the previous column, A(jj) + 1; a run of e extends keeps A(jj) + 1 + e
+//      -> H tags in [A + 1, A + Hmax] (at most Hmax - 1 extends, layt_ok's bound)
+//   V: open at slot s = G(s - 1) + KV(s), tag A + KVB + RPL - s; an extend keeps the tag of the
+//      slot that opened the run, which is larger -> V tags in [A + KVB, A + KVB + RPL - 1]
+//   diagonal candidate = G of the previous column + TDS = A + 1 + KVB + RPL - 1 = A + KVB + RPL
+// so D > V > H needs Hmax + 2 <= KVB (shift_ok; one tag to spare), and the largest tag, the
+// diagonal's at phase 0, is P + KVB + RPL - 1 = P + TDS <= 127. KVB and the largest period PMAX
+// are compile-time constants of the bucket (so KV(s) is a literal of the row's add): PMAX = 127 -
+// TDS trades against the longest H run Hmax <= KVB - 2; the default scheme's Hmax is (5 L + 3) / 2
+// + 1 (62 at 24 bp, 80 at 31 bp). A rebase (every P columns) adds ge P to the scores and P to the
+// tags of the stored keys: phase P - 1 becomes phase -1.
+template <int RPL>
+struct LayS : LayT<RPL> {
+    using T = LayT<RPL>;
+    static constexpr int PMAX = RPL <= 24 ? 32 : (RPL <= 28 ? 16 : 8);
+    static constexpr int TDS = 127 - PMAX;              // diagonal tag offset
+    static constexpr int KVB = TDS - RPL + 1;           // V-open tag offset of slot RPL
+    static constexpr int32_t TD_K = TDS << T::TB_SH;
+    static constexpr int32_t TAGM = 127 << T::TB_SH;    // the whole tag field
+    static constexpr int32_t SENT = (int32_t)0x80000000;   // score -128, below every shifted value
+    static constexpr int32_t kv(int s) { return (int32_t)(KVB + RPL - s) << T::TB_SH; }
+};
 constexpr int MAX_RPL = 88;
 constexpr int MAX_L = 88;
 constexpr int MAX_L_LONG = 128;
+// keys are added modulo 2^32 where a frame constant may wrap the score field on its own (the sum
+// is a key in range)
+PCABI_HD int32_t addw(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+PCABI_HD int32_t negw(int32_t a) { return (int32_t)(0u - (uint32_t)a); }
 // The sentinel NEG (H(., 0), V(0, .)) only ever competes in column 1 (H-extend vs H-open from
 // S(i, 0) = 0) and row 1 (V-extend vs V-open from S(0, j) = 0): it must lose there, NEG + ge <
 // gap_open, and nothing else (after those maxes every value is a real DP value).
@@ -1098,6 +1138,66 @@ PCABI_HD bool layt_ok(int L, int rpl, const Scoring &s) {
     if (lo < Y::SC_MIN || hi > Y::SC_MAX) return false;
     const long long smax = hi;
     return (smax - smin) / (-(long long)s.ge) + 1 < Y::TD - rpl;
+}
+
+// Range conditions of the gap-extend frame (pk::LayS) for an adapter of L bases in register bucket
+// rpl with rebase period P: the biases B in [blo, bhi] keep every shifted key's score inside the
+// 8-bit field, strictly above the -128 sentinel. false: none does, or the tags do not fit.
+//   * layt_ok holds (the last column runs LayT itself; its H-run bound is the one used here);
+//   * tags: Hmax + 2 <= KVB with Hmax = (Smax - Smin) / |ge| + 1 as in layt_ok, and 2 <= P <= PMAX
+//     (P >= 2: the column-0 H keys are gone before the first rebase moves the stored keys);
+//   * scores. Real row i = s - off of slot s (i <= 0: padding, S = 0 there as in row 0). In LayT's
+//     frame, with Slo(i) = go + (i - 1) ge (the vertical path from row 0; 0 for i <= 0) and
+//     Shi(i) = i max(best_sub, 0) (0 for i <= 0), Slo nonincreasing and Shi nondecreasing in i:
+//         S(i, .)       in [Slo(i),                Shi(i)]
+//         G = S + OPEN  in [Slo(i) + go - ge,      Shi(i) + go - ge]
+//         H(i, .)       in [Slo(i) + go,           Shi(i) + go]       (an open from S of the row;
+//                           column 0 holds neg_score = go - ge - 1 >= go, below max(go - ge, 0))
+//         V(i, .)       in [Slo(i - 1) + go,       Shi(i - 1) + go]   (an open from a row above)
+//         diagonal      in [Slo(i - 1) + min(ma, mi, 0), Shi(i - 1) + max(best_sub, 0)]
+//     A key of slot s is stored or used at phases -1 (after a rebase) .. P - 1, so its shifted
+//     score lies in [lo + |ge| (s - 1) - B, hi + |ge| (s + P - 1) - B]; row 0 (s = 0) holds G only.
+PCABI_HD int shift_pmax(int rpl) { return rpl <= 24 ? 32 : (rpl <= 28 ? 16 : 8); }
+PCABI_HD bool shift_range(int L, int rpl, const Scoring &s, int P, int &blo, int &bhi) {
+    if (!layt_ok(L, rpl, s)) return false;
+    const int pmax = shift_pmax(rpl), kvb = 127 - pmax - rpl + 1;
+    if (P < 2 || P > pmax) return false;
+    const int e = -s.ge, bs = best_sub(s) > 0 ? best_sub(s) : 0;
+    int msub = s.mi < s.ma ? s.mi : s.ma;
+    if (msub > 0) msub = 0;
+    const int smin = s.go + (L - 1) * s.ge, smax = L * bs;
+    if ((smax - smin) / e + 1 + 2 > kvb) return false;
+    const int off = rpl - L;
+    int lo0 = s.go, hi0 = s.go + e + e * (P - 1);     // row 0: G = OPEN
+    for (int sl = 1; sl <= rpl; ++sl) {
+        const int i = sl - off;
+        const int slo = i >= 1 ? s.go + (i - 1) * s.ge : 0, shi = i >= 1 ? i * bs : 0;
+        const int ulo = i >= 2 ? s.go + (i - 2) * s.ge : 0, uhi = i >= 2 ? (i - 1) * bs : 0;
+        int lo = slo + s.go;                          // H; S, G and the column-0 key lie above (go < 0)
+        if (ulo + msub < lo) lo = ulo + msub;         // diagonal; V lies above H (Slo(i - 1) >= Slo(i))
+        int hi = shi + (s.go + e > 0 ? s.go + e : 0); // S, G; H and V lie below
+        if (uhi + bs > hi) hi = uhi + bs;             // diagonal
+        lo += e * (sl - 1);
+        hi += e * (sl + P - 1);
+        if (lo < lo0) lo0 = lo;
+        if (hi > hi0) hi0 = hi;
+    }
+    blo = hi0 - 127;                                  // hi0 - B <= 127
+    bhi = lo0 + 127;                                  // lo0 - B >= -127
+    return blo <= bhi;
+}
+// The largest period (a power of two) with a bias, and the bias that centres the range; false:
+// the bucket keeps LayT for this adapter.
+PCABI_HD bool shift_ok(int L, int rpl, const Scoring &s, int &P, int &B) {
+    for (int p = shift_pmax(rpl); p >= 2; p >>= 1) {
+        int blo, bhi;
+        if (shift_range(L, rpl, s, p, blo, bhi)) {
+            P = p;
+            B = (blo + bhi) / 2;
+            return true;
+        }
+    }
+    return false;
 }
 
 PCABI_HD bool packed_ok(int L, int rpl, const Scoring &s) {
@@ -1381,6 +1481,191 @@ PCABI_HD Result align_lane_packed(ReadFn &rd, int n, const TabFn &tabfn, int L, 
     int n_fin;
     const Best b = packed_best<RPL, AFFINE, CHUNK, Y>(rd, n, tabfn, L, sc, own_lo, own_hi, n_fin);
     return finish(b, L, n_fin);
+}
+
+// ==========================================================================================
+// align_lane_shift<RPL>: the run-tagged core in the gap-extend frame (pk::LayS), for the cross-mode
+// launches of the affine buckets of <= 32 rows whose adapters all pass shift_ok. The inner columns
+// run in the frame -- per cell 4 full-rate VALU ops (V open, G, the next row's diagonal, the tag
+// mask) and 3 maxes, against LayT's 6 + 3; the frame's constants change once per column and are
+// uniform -- and their row-L scout keeps the best key in LayT's frame. Before the last column the
+// stored keys are taken back to LayT keys, and LanePacked<.., LayT>'s last column and finish()
+// run unchanged (their table rows are the frame's substitution keys less a constant, ShiftRow).
+// Same scores and the same winner in every max as LayT, so the results are identical.
+// ==========================================================================================
+namespace pk {
+// The diagonal step into slot s, added to G of slot s - 1 at the previous column (S + OPEN, tag
+// A(jj) + 1): sub - OPEN - 2 ge = sub - go - ge in the frame, the tag raised by TDS.
+template <int RPL, typename AdpFn>
+PCABI_HD int32_t sub_key_shift(int s, int c, const AdpFn &adp, int off, const Scoring &sc) {
+    using Y = LayS<RPL>;
+    if (s <= off) return Y::TD_K + Y::sc(-sc.go - sc.ge);
+    return (c == adp(s)) ? (Y::sc(sc.ma - sc.go - sc.ge) + Y::TD_K + Y::INC_M)
+                         : (Y::sc(sc.mi - sc.go - sc.ge) + Y::TD_K + Y::INC_D);
+}
+// A row of the frame's table read as LayT's: sub_key<LayT> = sub_key_shift + d for every slot and
+// code, d = sc(ge) + ((127 - TDS) << TB_SH).
+template <typename TabRow>
+struct ShiftRow {
+    TabRow t;
+    int32_t d;
+    PCABI_HD int32_t operator()(int s) const { return addw(t(s), d); }
+    PCABI_HD void quad(int q, int32_t *dst) const {
+        t.quad(q, dst);
+        for (int k = 0; k < 4; ++k) dst[k] = addw(dst[k], d);
+    }
+};
+}  // namespace pk
+
+template <int RPL, int PD = PCABI_TAB_PD>
+struct LaneShift {
+    using Y = pk::LayS<RPL>;
+    LanePacked<RPL, true, pk::LayT<RPL>, PD> st;   // G, HK, bkey, bj: the frame's keys until to_layt()
+    int32_t kgo;     // sc(OPEN) + (A(jj) << TB_SH): S key (tag cleared) -> stored G of this column
+    int32_t ftop;    // sc(f(0, jj)): uniform
+    int32_t k_e;     // sc(|ge|)
+    int32_t k_eR;    // sc(|ge| RPL)
+    int32_t k_rb;    // a rebase's score part: sc(ge P)
+    int jj, P;
+
+    PCABI_HD void init(int L, const Scoring &sc, int P_, int B) {
+        using pk::addw;
+        const int off = RPL - L;
+        P = P_;
+        jj = 0;
+        k_e = Y::sc(-sc.ge);
+        k_eR = Y::sc(-sc.ge * RPL);
+        k_rb = Y::sc(sc.ge * P);
+        ftop = Y::sc(-B);
+        kgo = Y::sc(sc.go - sc.ge) + ((P - 1) << Y::TB_SH);
+        int32_t fs = addw(ftop, kgo);              // sc(f(s, 0) + OPEN), tag A(0)
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            fs = addw(fs, k_e);
+            st.G[s] = addw(Y::start(off - s), fs);   // S(s, 0) = 0; padded (s, 0) reaches real (0, off - s)
+            // H(s, 0) = neg_score, tag A(0) + 1 (a run just opened: to_layt() gives LayT's column-0
+            // key back when the window has one column): it loses to G in column 1
+            st.HK[s] = addw(fs, Y::sc(-1) + Y::TAG1);
+        }
+        st.bkey = Y::start(-L);                    // the (L, 0) seed, LayT's frame
+        st.bj = 0;
+    }
+
+    // next column's phase: one column on, a rebase every P columns (uniform branch)
+    PCABI_HD void advance() {
+        using pk::addw;
+        ++jj;
+        kgo -= Y::TAG1;
+        ftop = addw(ftop, k_e);
+        if (jj == P) {
+            const int32_t rb = addw(k_rb, P << Y::TB_SH);
+#pragma unroll
+            for (int s = 1; s <= RPL; ++s) {
+                st.G[s] = addw(st.G[s], rb);
+                st.HK[s] = addw(st.HK[s], rb);
+            }
+            jj = 0;
+            kgo += P << Y::TB_SH;
+            ftop = addw(ftop, k_rb);
+        }
+    }
+
+    // inner column j at phase jj (after advance())
+    template <typename TabRow>
+    PCABI_HD void column(const TabRow &tab, const int j, const int off) {
+        using pk::addw;
+        const int32_t kg = vreg(kgo);              // the cell's add reads a VGPR (vreg)
+        const int32_t top = addw(ftop, kgo);
+        int32_t gup = addw(Y::start(j + off), top);            // G(0, j): S = 0, tag A(jj)
+        int32_t vup = Y::SENT;                                  // V(0, j)
+        // G(0, j - 1) in the frame of phase jj - 1: f lower by |ge|, tag A(jj) + 1
+        int32_t diag = addw(addw(Y::start(j - 1 + off), top), Y::TAG1 - k_e);
+        constexpr int NQ = RPL / 4;
+        int32_t t[RPL + 2];
+        if (PD > 0) {
+#pragma unroll
+            for (int q = 0; q <= PD && q < NQ; ++q) tab.quad(q, t + 4 * q + 1);
+        }
+        diag += (PD > 0 ? t[1] : tab(1));
+        int32_t lv = 0, ls = 0;
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            if (PD > 0 && (s & 3) == 1) {
+                const int q = (s - 1) / 4 + PD + 1;
+                if (q < NQ) tab.quad(q, t + 4 * q + 1);
+            }
+            int32_t diag_nx = 0;
+            if (s < RPL) diag_nx = st.G[s] + (PD > 0 ? t[s + 1] : tab(s + 1));
+            const int32_t hn = std::max(st.HK[s], st.G[s]);    // extend: the key itself; older tag wins ties
+            const int32_t vo = gup + Y::kv(s);
+            const int32_t vn = std::max(vup, vo);
+            const int32_t sn = max3i(diag, vn, hn);
+            if (s == RPL) { lv = vn; ls = sn; }
+            st.G[s] = (sn & ~Y::TAGM) + kg;
+            st.HK[s] = hn;
+            gup = st.G[s];
+            vup = vn;
+            diag = diag_nx;
+#if defined(__HIP_DEVICE_COMPILE__)
+            if (PCABI_ROW_FENCE > 0 && (s % (PCABI_ROW_FENCE > 0 ? PCABI_ROW_FENCE : 1)) == 0) __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
+        // row-L scout (LanePacked::column_tail): V tags are > 0, the S key's tag is cleared; the
+        // corrected key goes back to LayT's frame (score less f(RPL, jj); the tag only tells V from S)
+        const int32_t corr = addw(std::max(lv, ls & ~Y::TAGM), pk::negw(addw(ftop, k_eR)));
+        const bool upd = corr > (st.bkey | ((1 << Y::SC_SH) - 1));
+        st.bkey = upd ? corr : st.bkey;
+        st.bj = upd ? j : st.bj;
+    }
+
+    // The stored keys of phase jj as LayT keys: the score less f(s, jj), G's gap open go instead of
+    // OPEN and its tag cleared, the H tag less A(jj) + 1 (0 = just opened, e after e extends).
+    PCABI_HD void to_layt(const Scoring &sc) {
+        using pk::addw;
+        using pk::negw;
+        const int32_t tagA = kgo - Y::sc(sc.go - sc.ge);        // A(jj) << TB_SH
+        int32_t cg = addw(negw(addw(ftop, kgo)), Y::sc(sc.go));
+        int32_t ch = negw(addw(ftop, tagA + Y::TAG1));
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            cg = addw(cg, negw(k_e));
+            ch = addw(ch, negw(k_e));
+            st.G[s] = addw(st.G[s], cg);
+            st.HK[s] = addw(st.HK[s], ch);
+        }
+    }
+};
+
+template <int RPL, int PD = PCABI_TAB_PD, typename ReadFn, typename TabFn>
+PCABI_HD Result align_lane_shift(ReadFn &rd, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
+    using Y = pk::LayS<RPL>;
+    LaneShift<RPL, PD> ls;
+    const int off = RPL - L;
+    ls.init(L, sc, P, B);
+    int r = rd(1);
+#pragma unroll 1
+    for (int j = 1; j < n; ++j) {
+        const int rn = rd(j + 1);
+        ls.advance();
+        ls.template column<decltype(tabfn(r))>(tabfn(r), j, off);
+        r = rn;
+    }
+    ls.to_layt(sc);
+    auto &st = ls.st;
+    const int32_t neg = Y::sc(pk::neg_score(sc));
+    st.k_ge = vreg(Y::sc(sc.ge));
+    st.k_go = vreg(Y::sc(sc.go));
+    st.k_gev = st.k_geh = 0;
+    st.k_gex = vreg(Y::sc(sc.ge) + Y::TB1);
+    st.k_vo = Y::TB2;
+    st.neg2 = neg | Y::TB2;
+    st.materialize(L);
+    const pk::ShiftRow<decltype(tabfn(r))> row{tabfn(r), Y::sc(sc.ge) + ((127 - Y::TDS) << Y::TB_SH)};
+    st.template column<decltype(row), true>(row, n, L, off);
+    Best b;
+    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
+    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
+    return finish(b, L, n);
 }
 
 // Long buckets: pass 0 (c, nD) and pass 1 (m) over the same window (two readers, two tables);

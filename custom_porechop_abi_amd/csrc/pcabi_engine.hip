@@ -1253,6 +1253,33 @@ int bucket_pack_mode(int b, const std::vector<int32_t> &lens, const pcabi::Scori
     return 2;
 }
 
+// Whether a cross-mode launch of a run-tagged bucket (bucket_pack_mode 2) runs its inner columns in
+// the gap-extend frame (pcabi_dp.h pk::LayS): every adapter passes shift_ok, at one period (the
+// largest every adapter allows) and one bias (the middle of the ranges' intersection). Sets
+// p.shift_p / p.shift_b (0: the bucket keeps LayT). The chunk, split and pairs launches keep LayT.
+void bucket_shift(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc, int pack_mode, KParams &p) {
+    p.shift_p = p.shift_b = 0;
+    if (pack_mode != 2 || lens.empty() || sc.go == sc.ge) return;
+    const char *e = std::getenv("PCABI_SHIFT");   // PCABI_SHIFT=0: every bucket keeps LayT (A/B measurements)
+    if (e && e[0] == '0') return;
+    const int rpl = kBuckets[b].rpl;
+    for (int P = pcabi::shift_pmax(rpl); P >= 2; P >>= 1) {
+        int lo = INT32_MIN, hi = INT32_MAX;
+        bool ok = true;
+        for (int32_t L : lens) {
+            int blo, bhi;
+            if (!pcabi::shift_range(L, rpl, sc, P, blo, bhi)) { ok = false; break; }
+            lo = std::max(lo, blo);
+            hi = std::min(hi, bhi);
+        }
+        if (ok && lo <= hi) {
+            p.shift_p = P;
+            p.shift_b = lo + (hi - lo) / 2;
+            return;
+        }
+    }
+}
+
 // Host-side layout of a bucket's adapter table.
 struct BucketHost {
     std::vector<uint8_t> pad;   // n * RPL bytes (striped: n * rt)
@@ -1864,7 +1891,11 @@ int align_host_impl(int device, const uint8_t *codes, int64_t codes_len, const i
                 p.tile_off = (const int64_t *)e.toff.p;
             }
             // launched below, side by side once every bucket's table is on its way
-            if (n_win > 0) cross.push_back({b, p, bucket_pack_mode(b, h.len, sc)});
+            if (n_win > 0) {
+                const int pack = bucket_pack_mode(b, h.len, sc);
+                bucket_shift(b, h.len, sc, pack, p);
+                cross.push_back({b, p, pack});
+            }
         } else {
             tw.clear(); to.clear(); wa.clear();
             for (int k = 0; k < nb; ++k) {
@@ -2600,7 +2631,9 @@ int pcabi_align_cross_dev_marked(const uint32_t *tiles, const int64_t *tile_off,
         const hipStream_t st = fj.at(k);
         // the largest bucket runs on the caller's stream (k == 0): the optional events bracket it
         if (k == 0 && ev_begin) HIP_TRY(hipEventRecord((hipEvent_t)ev_begin, st));
-        if (int rc = dispatch(b, p, affine, st, bucket_pack_mode(b, adps->lens[b], p.sc))) {
+        const int pack = bucket_pack_mode(b, adps->lens[b], p.sc);
+        bucket_shift(b, adps->lens[b], p.sc, pack, p);
+        if (int rc = dispatch(b, p, affine, st, pack)) {
             (void)fj.end();
             return rc;
         }
@@ -2650,6 +2683,7 @@ int pcabi_align_cross_multi_dev(const pcabi_cross_region *regions, int32_t n_reg
             p.adp_id = adps->id[b];
             p.n_adp = adps->count[b];
             p.rt = adps->rt[b];
+            bucket_shift(b, adps->lens[b], sc, u.pack, p);
             u.blocks = (g.n_win + 8 * 256 - 1) / (8 * 256) * 8 * (int64_t)p.n_adp;
             u.cost = (g.n_win + 255) / 256 * (int64_t)p.n_adp * kBuckets[b].rpl;
             units.push_back(u);
@@ -2691,6 +2725,8 @@ int pcabi_align_cross_multi_dev(const pcabi_cross_region *regions, int32_t n_reg
                 s.out = u.p.out;
                 s.out_stride = u.p.out_stride;
                 s.rpl = kBuckets[u.b].rpl;
+                s.shift_p = u.p.shift_p;
+                s.shift_b = u.p.shift_b;
                 s.block0 = l.blocks;
                 l.blocks += u.blocks;
                 l.cost += u.cost;

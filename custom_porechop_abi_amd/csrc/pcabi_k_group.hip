@@ -2,7 +2,8 @@
 // units of one core family, each a (window set, register bucket) cross product, in one launch.
 // The block's unit is found by a scalar walk over the segment table in the kernel arguments; the
 // unit's rows select the core (a wave-uniform switch), which then runs exactly as k_align's cross
-// mode (cross_block). The kernel's register count is its largest case's: class 0 (run-tagged, <= 32
+// mode (cross_block); a class-0 unit whose adapters all pass pcabi::shift_ok runs in the gap-extend
+// frame (GroupSeg::shift_p > 0). The kernel's register count is its largest case's: class 0 (run-tagged, <= 32
 // rows) holds 5 waves per SIMD, class 1 (packed, 36..64 rows) 3.
 #include "pcabi_kern.h"
 
@@ -29,12 +30,22 @@ __global__ __launch_bounds__(256) void k_align_group(GroupParams gp) {
     p.out = g.out;
     p.out_stride = g.out_stride;
     p.sc = gp.sc;
+    p.shift_p = g.shift_p;
+    p.shift_b = g.shift_b;
     const int64_t lb = b - g.block0;
     if constexpr (CLS == 0) {
-        switch (g.rpl) {
-#define T(R) case R: cross_block<R, true, TAGGED>(p, lb, wave_tab); break;
-        T(4) T(8) T(12) T(16) T(20) T(24) T(28) T(32)
+        if (g.shift_p > 0) {
+            switch (g.rpl) {
+#define T(R) case R: cross_block<R, true, SHIFT>(p, lb, wave_tab); break;
+            T(4) T(8) T(12) T(16) T(20) T(24) T(28) T(32)
 #undef T
+            }
+        } else {
+            switch (g.rpl) {
+#define T(R) case R: cross_block<R, true, TAGGED>(p, lb, wave_tab); break;
+            T(4) T(8) T(12) T(16) T(20) T(24) T(28) T(32)
+#undef T
+            }
         }
     } else {
         switch (g.rpl) {
