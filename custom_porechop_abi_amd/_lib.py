@@ -146,6 +146,17 @@ def lib():
         'pcabi_bam_unpack_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
         'pcabi_bam_unpack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
         'pcabi_bam_last_times': ([c_int, c_int, c_p, c_p], None),
+        'pcabi_bgzf_scratch_bytes': ([c_i64, c_i64], c_i64),
+        'pcabi_bgzf_dev': ([c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64], c_int),
+        'pcabi_bam_pack_plan': ([c_p, c_i64, c_i64, c_p], c_i64),
+        'pcabi_bam_pack_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64], c_int),
+        'pcabi_bam_pack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_bam_pack_last_times': ([c_int, c_p, c_p], None),
+        'pcabi_reads_write_bam': ([c_p, ctypes.c_char_p, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p,
+                                   ctypes.c_char_p, c_i64, c_int, c_int], c_int),
+        'pcabi_fastx_keep_aux': ([c_p, c_int], c_int),
+        'pcabi_reads_aux': ([c_p, c_p, c_p, c_p], c_int),
+        'pcabi_fastx_bam_header': ([c_p, c_p, c_p], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -186,7 +197,9 @@ def exported_symbols():
             'pcabi_gunzip_index', 'pcabi_gunzip_scratch_bytes', 'pcabi_gunzip_dev', 'pcabi_gunzip_host',
             'pcabi_gunzip_tune', 'pcabi_gunzip_last_times', 'pcabi_bgzf_bound', 'pcabi_bgzf_host',
             'pcabi_bgzf_write_eof', 'pcabi_bam_index', 'pcabi_bam_unpack_dev', 'pcabi_bam_unpack_host',
-            'pcabi_bam_last_times']
+            'pcabi_bam_last_times', 'pcabi_bgzf_scratch_bytes', 'pcabi_bgzf_dev', 'pcabi_bam_pack_plan',
+            'pcabi_bam_pack_dev', 'pcabi_bam_pack_host', 'pcabi_bam_pack_last_times', 'pcabi_reads_write_bam',
+            'pcabi_fastx_keep_aux', 'pcabi_reads_aux', 'pcabi_fastx_bam_header']
 
 
 class CrossRegion(ctypes.Structure):

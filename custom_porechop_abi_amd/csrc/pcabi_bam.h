@@ -1,4 +1,5 @@
-// pcabi_bam.h -- the record layer of unaligned BAM input (pcabi_bam.hip, pcabi_io.cpp): the header
+// pcabi_bam.h -- the record layer of unaligned BAM input and output (pcabi_bam.hip, pcabi_io.cpp; the
+// pack half for output is at the end of the file). Input: the header
 // skip, the record walk and the unpack of one record's bases into the reader's batch layout (sequence
 // letters, qualities, Dna5 codes). Nothing here is device-only: the kernel (k_bam_unpack), the host
 // reader and the CPU tests (tests/bam_fuzz_main.cpp builds it alone) run the same code.
@@ -248,6 +249,174 @@ PCABI_HD inline bool rec_fits(const pcabi_bam_rec &r, int64_t n, int64_t seq_cap
     if (l < 0 || r.rec < 0 || r.seq_at < 0 || r.seq_out < 0 || r.qual_out < 0 || r.code_out < 0) return false;
     if (r.rec > n || r.seq_at > n - r.rec || (l + 1) / 2 + l > n - r.rec - r.seq_at) return false;
     return l <= seq_cap - r.seq_out && l <= qual_cap - r.qual_out && ((l + 3) & ~(int64_t)3) <= codes_cap - r.code_out;
+}
+
+// ---- pack (BAM output) ---------------------------------------------------------------------------
+// The inverse of the unpack: parts of a batch (include/pcabi.h pcabi_bam_part) laid out as a chain of
+// unmapped records. The kernel (k_bam_pack), the host writer and the CPU tests
+// (tests/bam_pack_fuzz_main.cpp builds it alone) run the same code.
+
+constexpr int kMaxName = 254;   // l_read_name is a byte and counts the NUL
+
+PCABI_HD inline int64_t part_size(const pcabi_bam_part &p) {
+    return 4 + kFixed + ((int64_t)p.name_len + 1) + ((int64_t)p.l_seq + 1) / 2 + (int64_t)p.l_seq + (int64_t)p.aux_len;
+}
+PCABI_HD inline int64_t part_tiles(const pcabi_bam_part &p) {
+    const int64_t t = ((int64_t)p.l_seq + kTileBases - 1) / kTileBases;
+    return t > 0 ? t : 1;   // a record without bases still has a header to write
+}
+// where a part's packed sequence starts, from the record's start
+PCABI_HD inline int64_t part_seq_at(const pcabi_bam_part &p) { return 4 + kFixed + (int64_t)p.name_len + 1; }
+
+// Output offsets and tiles of the next part of the chain.
+struct PackLayout {
+    int64_t out = 0, tiles = 0;
+    PCABI_HD void place(pcabi_bam_part *p) {
+        p->out = out;
+        p->tile0 = tiles;
+        out += part_size(*p);
+        tiles += part_tiles(*p);
+    }
+};
+
+// Letter -> code over "=ACMGRSVTWYHKDBN" (U -> T, anything else -> N): a nibble per letter of 'A'..'P'
+// and 'Q'..'`' in two registers.
+constexpr uint64_t kCodeAP = 0xFFF3FCFFB4FFD2E1ull;
+constexpr uint64_t kCodeQ = 0xFFFFFFFAF978865Full;
+PCABI_HD inline uint32_t code_of(uint32_t c) {
+    const uint32_t u = c - 65u;
+    if (u < 16u) return (uint32_t)(kCodeAP >> (4 * u)) & 15u;
+    if (u < 32u) return (uint32_t)(kCodeQ >> (4 * (u - 16u))) & 15u;
+    return c == '=' ? 0u : 15u;
+}
+PCABI_HD inline uint8_t phred_of(uint32_t c) { return (uint8_t)(c < 33u ? 0u : c > 126u ? 93u : c - 33u); }
+
+// Output bases [b0, b1) of one part: src / qsrc = its letters and quality characters (qsrc nullptr:
+// absent, 0xFF), l_seq its length, sq / ql = where the record's packed sequence and its qualities
+// start, or nullptr to leave that output alone. With sq, b0 is even (tile and piece edges fall on even
+// base counts, so no packed byte has two writers; an odd b0 writes no sequence byte). Stores are 16 bytes wide where the destination is
+// 16-aligned and the range covers them, single bytes at the ragged ends; nothing outside the range's
+// own packed-sequence bytes [b0 / 2, (b1 + 1) / 2) and quality bytes [b0, b1) is written.
+PCABI_HD inline void pack_range(const uint8_t *src, const uint8_t *qsrc, int32_t l_seq32, int64_t b0, int64_t b1,
+                                uint8_t *sq, uint8_t *ql) {
+    const int64_t l_seq = l_seq32;
+    if (b1 > l_seq) b1 = l_seq;
+    if (b0 < 0) b0 = 0;
+    if (b0 >= b1) return;
+    if (sq && !(b0 & 1)) {
+        const int64_t e = (b1 + 1) / 2;   // bytes [p, e)
+        auto byte_at = [&](int64_t p) {
+            const uint32_t hi = code_of(src[2 * p]), lo = 2 * p + 1 < l_seq ? code_of(src[2 * p + 1]) : 0u;
+            return (uint8_t)(hi << 4 | lo);
+        };
+        int64_t p = b0 / 2;
+        for (; p < e && !(aligned16(sq + p) && 2 * (p + 16) <= b1); ++p) sq[p] = byte_at(p);
+        for (; 2 * (p + 16) <= b1; p += 16) {
+            uint8_t c[32], v[16];
+            memcpy(c, src + 2 * p, 32);
+PCABI_BAM_UNROLL
+            for (int k = 0; k < 16; ++k) v[k] = (uint8_t)(code_of(c[2 * k]) << 4 | code_of(c[2 * k + 1]));
+            store16(sq + p, v);
+        }
+        for (; p < e; ++p) sq[p] = byte_at(p);
+    }
+    if (ql) {
+        int64_t p = b0;
+        for (; p < b1 && !(aligned16(ql + p) && p + 16 <= b1); ++p) ql[p] = qsrc ? phred_of(qsrc[p]) : (uint8_t)0xff;
+        for (; p + 16 <= b1; p += 16) {
+            uint8_t q[16], v[16];
+            if (qsrc) {
+                memcpy(q, qsrc + p, 16);
+PCABI_BAM_UNROLL
+                for (int k = 0; k < 16; ++k) v[k] = phred_of(q[k]);
+            } else {
+PCABI_BAM_UNROLL
+                for (int k = 0; k < 16; ++k) v[k] = 0xff;
+            }
+            store16(ql + p, v);
+        }
+        for (; p < b1; ++p) ql[p] = qsrc ? phred_of(qsrc[p]) : (uint8_t)0xff;
+    }
+}
+
+// Byte k of a record's block_size and fixed fields (k in [0, 36)).
+PCABI_HD inline uint8_t head_byte(const pcabi_bam_part &p, int k) {
+    const uint32_t block = (uint32_t)(part_size(p) - 4), l = (uint32_t)p.l_seq;
+    if (k < 4) return (uint8_t)(block >> (8 * k));
+    if (k < 12) return 0xff;                                   // refID, pos = -1
+    if (k == 12) return (uint8_t)(p.name_len + 1);             // l_read_name
+    if (k == 13) return 0;                                     // mapq
+    if (k < 16) return (uint8_t)(4680u >> (8 * (k - 14)));     // bin
+    if (k < 18) return 0;                                      // n_cigar_op
+    if (k < 20) return (uint8_t)(4u >> (8 * (k - 18)));        // flag: unmapped
+    if (k < 24) return (uint8_t)(l >> (8 * (k - 20)));         // l_seq
+    if (k < 32) return 0xff;                                   // next_refID, next_pos = -1
+    return 0;                                                  // tlen
+}
+
+// Everything of a record but its bases: block_size, fixed fields, name, NUL and the aux bytes, as byte
+// copies k = first, first + step, ... (the kernel strides them over the lanes; the host passes 0, 1).
+PCABI_HD inline void pack_head(const pcabi_bam_part &p, const uint8_t *side, uint8_t *rec, int64_t first, int64_t step) {
+    const int64_t head = 4 + kFixed, nm = p.name_len, aux_at = part_seq_at(p) + ((int64_t)p.l_seq + 1) / 2 + p.l_seq;
+    const uint8_t *s = side + p.side_off;
+    for (int64_t k = first; k < head; k += step) rec[k] = head_byte(p, (int)k);
+    for (int64_t k = first; k <= nm; k += step) rec[head + k] = k < nm ? s[k] : (uint8_t)0;
+    for (int64_t k = first; k < p.aux_len; k += step) rec[aux_at + k] = s[nm + k];
+}
+
+// One whole part (the host build): seq / qual / side / out are the buffers' starts.
+inline void pack_part(const pcabi_bam_part &p, const uint8_t *seq, const uint8_t *qual, const uint8_t *side, uint8_t *out) {
+    uint8_t *rec = out + p.out, *sq = rec + part_seq_at(p);
+    pack_head(p, side, rec, 0, 1);
+    pack_range(seq + p.seq_src, p.qual_src >= 0 ? qual + p.qual_src : nullptr, p.l_seq, 0, p.l_seq, sq,
+               sq + ((int64_t)p.l_seq + 1) / 2);
+}
+
+// A part against the buffers it names.
+PCABI_HD inline bool part_fits(const pcabi_bam_part &p, int64_t seq_n, int64_t qual_n, int64_t side_n, int64_t out_cap) {
+    const int64_t l = p.l_seq;
+    if (l < 0 || p.name_len < 0 || p.name_len > kMaxName || p.aux_len < 0 || p.seq_src < 0 || p.side_off < 0 || p.out < 0 ||
+        p.tile0 < 0)
+        return false;
+    if (l > seq_n - p.seq_src || (p.qual_src >= 0 && l > qual_n - p.qual_src)) return false;
+    if ((int64_t)p.name_len + p.aux_len > side_n - p.side_off) return false;
+    return part_size(p) <= out_cap - p.out;
+}
+
+// The tag at a[at, n) of an aux chain: the offset behind it, or -1 when its type is not one of
+// A c C s S i I f Z H B or it runs past n.
+PCABI_HD inline int64_t aux_next(const uint8_t *a, int64_t n, int64_t at) {
+    if (at < 0 || n - at < 3) return -1;
+    auto width = [](uint8_t t) { return t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0; };
+    const uint8_t t = a[at + 2];
+    int64_t q = at + 3;
+    if (t == 'A') return n - q >= 1 ? q + 1 : -1;
+    if (width(t)) return n - q >= width(t) ? q + width(t) : -1;
+    if (t == 'Z' || t == 'H') {
+        for (; q < n; ++q)
+            if (a[q] == 0) return q + 1;
+        return -1;
+    }
+    if (t == 'B') {
+        if (n - q < 5 || !width(a[q])) return -1;
+        const int64_t count = (uint32_t)le32(a + q + 1), bytes = count * width(a[q]);
+        return bytes <= n - q - 5 ? q + 5 + bytes : -1;
+    }
+    return -1;
+}
+// Whether a[0, n) is a chain of whole tags.
+PCABI_HD inline bool aux_walks(const uint8_t *a, int64_t n) {
+    int64_t at = 0;
+    while (at < n) {
+        at = aux_next(a, n, at);
+        if (at < 0) return false;
+    }
+    return true;
+}
+// Tags whose values count bases of the stored sequence: dropped from a read that was changed.
+PCABI_HD inline bool aux_positional(const uint8_t *tag) {
+    return (tag[0] == 'M' && (tag[1] == 'M' || tag[1] == 'L' || tag[1] == 'N' || tag[1] == 'm' || tag[1] == 'l')) ||
+           (tag[0] == 'm' && tag[1] == 'v');
 }
 
 }  // namespace pcabi_bam

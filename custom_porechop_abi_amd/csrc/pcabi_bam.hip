@@ -1,5 +1,5 @@
-// pcabi_bam.hip -- unaligned BAM records unpacked on the GPU (gfx950): include/pcabi.h pcabi_bam_*;
-// DESIGN.md "BAM input".
+// pcabi_bam.hip -- unaligned BAM records unpacked (k_bam_unpack) and packed (k_bam_pack, further down)
+// on the GPU (gfx950): include/pcabi.h pcabi_bam_*; DESIGN.md "BAM input", "BAM output".
 //
 // k_bam_unpack: the packed 4-bit sequence and the raw qualities of every record in a table the host
 // built (pcabi_bam.h walk) become sequence letters, qualities + 33 and Dna5 codes in the reader's
@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -90,6 +91,66 @@ int launch(hipStream_t st, const uint8_t *bam, int64_t n, const pcabi_bam_rec *r
     return 0;
 }
 
+// k_bam_pack: the inverse (DESIGN.md "BAM output"). A table of parts (pcabi_bam.h PackLayout) becomes a
+// chain of unmapped BAM records: one workgroup per tile of 16384 bases, the part found by the same
+// uniform binary search over tile0. Every part owns at least one tile, a part without bases too: the
+// workgroup of a part's first tile also writes block_size, the fixed fields, the name with its NUL and
+// the aux bytes, as byte copies striding over the lanes. The packed sequence (two letters a byte) and
+// the qualities (character - 33) are cut where the destination is 16-byte aligned, as in the unpack:
+// a lane loads a piece's 32 letters or 16 quality characters and stores sixteen aligned bytes; the
+// ragged first and last pieces are single bytes. Tile edges are even base counts, so no packed byte
+// has two writers. A part writes its own record's bytes only.
+__global__ __launch_bounds__(kLanes) void k_bam_pack(const uint8_t *__restrict__ seq, int64_t seq_n,
+                                                     const uint8_t *__restrict__ qual, int64_t qual_n,
+                                                     const uint8_t *__restrict__ side, int64_t side_n,
+                                                     const pcabi_bam_part *__restrict__ parts, int64_t n_parts,
+                                                     int64_t n_tiles, uint8_t *__restrict__ out, int64_t out_cap) {
+    const int64_t tile = blockIdx.x;
+    if (tile >= n_tiles || n_parts <= 0) return;
+    int64_t lo = 0, hi = n_parts - 1;   // the last part whose tile0 <= tile
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (parts[mid].tile0 <= tile) lo = mid;
+        else hi = mid - 1;
+    }
+    const pcabi_bam_part p = parts[lo];
+    if (!part_fits(p, seq_n, qual_n, side_n, out_cap)) return;   // uniform
+    const int64_t t0 = (tile - p.tile0) * kTileBases;
+    if (t0 < 0 || t0 >= part_tiles(p) * kTileBases) return;
+    uint8_t *rec = out + p.out;
+    if (t0 == 0) pack_head(p, side, rec, threadIdx.x, kLanes);
+    if (t0 >= p.l_seq) return;
+    const int64_t t1 = t0 + kTileBases < p.l_seq ? t0 + kTileBases : (int64_t)p.l_seq;
+    const uint8_t *src = seq + p.seq_src, *qsrc = p.qual_src >= 0 ? qual + p.qual_src : nullptr;
+    uint8_t *sq = rec + part_seq_at(p), *ql = sq + ((int64_t)p.l_seq + 1) / 2;
+    {   // packed sequence: bytes [t0 / 2, (t1 + 1) / 2) in pieces of the destination's 16-byte grid
+        const int64_t d = (int64_t)(uintptr_t)sq, y0 = t0 / 2, y1 = (t1 + 1) / 2;
+        const int64_t a = (d + y0) & ~(int64_t)15, pieces = (d + y1 - a + 15) >> 4;
+        for (int64_t k = threadIdx.x; k < pieces; k += kLanes) {
+            const int64_t q0 = a + 16 * k - d, c0 = q0 > y0 ? q0 : y0, c1 = q0 + 16 < y1 ? q0 + 16 : y1;
+            pack_range(src, qsrc, p.l_seq, 2 * c0, 2 * c1 < t1 ? 2 * c1 : t1, sq, nullptr);
+        }
+    }
+    {   // qualities: bytes [t0, t1)
+        const int64_t d = (int64_t)(uintptr_t)ql;
+        const int64_t a = (d + t0) & ~(int64_t)15, pieces = (d + t1 - a + 15) >> 4;
+        for (int64_t k = threadIdx.x; k < pieces; k += kLanes) {
+            const int64_t q0 = a + 16 * k - d, b0 = q0 > t0 ? q0 : t0, b1 = q0 + 16 < t1 ? q0 + 16 : t1;
+            pack_range(src, qsrc, p.l_seq, b0, b1, nullptr, ql);
+        }
+    }
+}
+
+int launch_pack(hipStream_t st, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const uint8_t *side,
+                int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts, int64_t n_tiles, uint8_t *out, int64_t out_cap) {
+    if (n_tiles < 0 || n_tiles >= INT32_MAX) return fail(PCABI_E_ARG, "too many tiles for one launch");
+    if (n_parts <= 0 || n_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_bam_pack, dim3((unsigned)n_tiles), dim3(kLanes), 0, st, seq, seq_n, qual, qual_n, side, side_n, parts,
+                       n_parts, n_tiles, out, out_cap);
+    BAM_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device-event spans (the timing tool) --------------------------------------------------------
 struct Span {
     hipEvent_t a = nullptr, b = nullptr;
@@ -98,8 +159,8 @@ struct Span {
 std::mutex g_prof_mu;
 bool g_prof = false;
 std::vector<Span *> g_spans;
-double g_ms[4] = {0, 0, 0, 0};
-int64_t g_unpack_bytes = 0;
+double g_ms[5] = {0, 0, 0, 0, 0};   // [4]: k_bam_pack
+int64_t g_unpack_bytes = 0, g_pack_bytes = 0;
 
 void harvest() {   // g_prof_mu held; the spans' streams are idle
     for (Span *s : g_spans) {
@@ -122,7 +183,7 @@ bool prof_on() {
     return g_prof;
 }
 
-// kind: 0 k_inflate, 1 k_bam_unpack, 2 copies to the device, 3 copies from the device
+// kind: 0 k_inflate, 1 k_bam_unpack, 2 copies to the device, 3 copies from the device, 4 k_bam_pack
 void *prof_begin(void *stream, int kind) {
     Span *s = new Span();
     s->kind = kind;
@@ -275,6 +336,126 @@ int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const L
     return 0;
 }
 
+// ---- the device half of the BAM writer (csrc/pcabi_io.cpp) ---------------------------------------
+// head[0, head_n) (the file header, or nothing) and the record chain of `parts` (planned from head_n)
+// form one stream of stream_n bytes in device memory: the text, the table and the side blob go up,
+// k_bam_pack writes the chain, the BGZF encoder (pcabi_bgzf_dev) reads it there in members of 65280
+// bytes, and only the compressed bytes come back, into pinned memory that `sink` reads before the call
+// returns. The buffers are kept between calls (one device at a time, one call at a time). Returns the
+// compressed length or a negative code.
+namespace {
+struct PackDev {
+    int device = -1;
+    uint8_t *buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // seq, qual, side, parts, stream, z
+    int64_t cap[6] = {0, 0, 0, 0, 0, 0};
+    void *scratch = nullptr;
+    int64_t scratch_cap = 0;
+    int64_t *d_len = nullptr;
+    uint8_t *p_z = nullptr;   // the compressed bytes, pinned
+    int64_t p_z_cap = 0;
+    hipStream_t st = nullptr;
+} g_pack;
+std::mutex g_pack_mu;
+
+void pack_dev_free() {
+    for (int k = 0; k < 6; ++k) {
+        if (g_pack.buf[k]) (void)hipFree(g_pack.buf[k]);
+        g_pack.buf[k] = nullptr;
+        g_pack.cap[k] = 0;
+    }
+    if (g_pack.scratch) (void)hipFree(g_pack.scratch);
+    if (g_pack.d_len) (void)hipFree(g_pack.d_len);
+    if (g_pack.p_z) (void)hipHostFree(g_pack.p_z);
+    g_pack.p_z = nullptr;
+    g_pack.p_z_cap = 0;
+    if (g_pack.st) (void)hipStreamDestroy(g_pack.st);
+    g_pack.scratch = nullptr;
+    g_pack.d_len = nullptr;
+    g_pack.st = nullptr;
+    g_pack.scratch_cap = 0;
+    g_pack.device = -1;
+}
+
+int pack_dev_room(uint8_t **p, int64_t *cap, int64_t need) {
+    if (*cap >= need) return 0;
+    if (*p) BAM_TRY(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const int64_t want = std::max<int64_t>(need + need / 4, 1 << 20);
+    BAM_TRY(hipMalloc((void **)p, (size_t)want));
+    *cap = want;
+    return 0;
+}
+}  // namespace
+
+int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
+                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink) {
+    std::lock_guard<std::mutex> lk(g_pack_mu);
+    if (device < 0) BAM_TRY(hipGetDevice(&device));
+    if (g_pack.device >= 0 && g_pack.device != device) {
+        (void)hipSetDevice(g_pack.device);
+        pack_dev_free();
+    }
+    BAM_TRY(hipSetDevice(device));
+    g_pack.device = device;
+    if (!g_pack.st) BAM_TRY(hipStreamCreateWithFlags(&g_pack.st, hipStreamNonBlocking));
+    if (!g_pack.d_len) BAM_TRY(hipMalloc((void **)&g_pack.d_len, 64));
+    hipStream_t st = g_pack.st;
+    const int64_t block = PCABI_BGZF_BLOCK_CAP;
+    const int64_t z_cap = pcabi_bgzf_bound(stream_n, std::max<int64_t>((stream_n + block - 1) / block, 1), 0);
+    const int64_t sc = pcabi_bgzf_scratch_bytes(stream_n, block);
+    if (z_cap < 0 || sc < 0) return z_cap < 0 ? z_cap : sc;
+    const int64_t need[6] = {seq_n + 64, qual_n + 64, side_n + 64, n_parts * (int64_t)sizeof(pcabi_bam_part) + 64,
+                             stream_n + 64, z_cap + 64};
+    for (int k = 0; k < 6; ++k)
+        if (int rc = pack_dev_room(&g_pack.buf[k], &g_pack.cap[k], need[k])) return rc;
+    if (g_pack.scratch_cap < sc) {
+        if (g_pack.scratch) BAM_TRY(hipFree(g_pack.scratch));
+        g_pack.scratch = nullptr;
+        g_pack.scratch_cap = 0;
+        BAM_TRY(hipMalloc(&g_pack.scratch, (size_t)sc + sc / 4));
+        g_pack.scratch_cap = sc + sc / 4;
+    }
+    uint8_t *d_seq = g_pack.buf[0], *d_qual = g_pack.buf[1], *d_side = g_pack.buf[2], *d_stream = g_pack.buf[4],
+            *d_z = g_pack.buf[5];
+    pcabi_bam_part *d_parts = (pcabi_bam_part *)g_pack.buf[3];
+    if (seq_n > 0) BAM_TRY(hipMemcpyAsync(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
+    if (qual_n > 0) BAM_TRY(hipMemcpyAsync(d_qual, qual, (size_t)qual_n, hipMemcpyHostToDevice, st));
+    if (side_n > 0) BAM_TRY(hipMemcpyAsync(d_side, side, (size_t)side_n, hipMemcpyHostToDevice, st));
+    if (n_parts > 0)
+        BAM_TRY(hipMemcpyAsync(d_parts, parts, (size_t)n_parts * sizeof(pcabi_bam_part), hipMemcpyHostToDevice, st));
+    if (head_n > 0) BAM_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
+    const bool prof = prof_on();
+    void *sp = prof ? prof_begin(st, 4) : nullptr;
+    if (int rc = launch_pack(st, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, n_tiles, d_stream, stream_n))
+        return rc;
+    if (prof) {
+        prof_end(st, sp);
+        std::lock_guard<std::mutex> pk(g_prof_mu);
+        for (int64_t i = 0; i < n_parts; ++i) g_pack_bytes += 2 * (int64_t)parts[i].l_seq + part_size(parts[i]);
+        g_pack_bytes += n_parts * (int64_t)sizeof(pcabi_bam_part);
+    }
+    if (int rc = pcabi_bgzf_dev(st, d_stream, stream_n, block, d_z, z_cap, g_pack.d_len, g_pack.scratch, g_pack.scratch_cap))
+        return rc;
+    int64_t zn = 0;
+    BAM_TRY(hipMemcpyAsync(&zn, g_pack.d_len, 8, hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipStreamSynchronize(st));
+    if (zn < 0 || zn > z_cap) return fail(PCABI_E_DEVICE, "the BGZF encoder refused the stream");
+    if (g_pack.p_z_cap < zn) {
+        if (g_pack.p_z) BAM_TRY(hipHostFree(g_pack.p_z));
+        g_pack.p_z = nullptr;
+        g_pack.p_z_cap = 0;
+        const int64_t want = std::max<int64_t>(zn + zn / 4, 1 << 20);
+        BAM_TRY(hipHostMalloc((void **)&g_pack.p_z, (size_t)want, hipHostMallocDefault));
+        g_pack.p_z_cap = want;
+    }
+    if (zn > 0) BAM_TRY(hipMemcpyAsync(g_pack.p_z, d_z, (size_t)zn, hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipStreamSynchronize(st));
+    sink(g_pack.p_z, zn);
+    return zn;
+}
+
 }  // namespace pcabi_internal
 
 extern "C" {
@@ -386,10 +567,98 @@ void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes) {
         for (int k = 0; k < 4; ++k) ms[k] = g_ms[k];
     if (bytes) *bytes = g_unpack_bytes;
     if (reset) {
-        for (double &v : g_ms) v = 0;
+        for (int k = 0; k < 4; ++k) g_ms[k] = 0;
         g_unpack_bytes = 0;
     }
     if (on >= 0) g_prof = on != 0;
+}
+
+int64_t pcabi_bam_pack_plan(pcabi_bam_part *parts, int64_t n_parts, int64_t out0, int64_t *tiles) {
+    if (n_parts < 0 || (n_parts > 0 && !parts) || out0 < 0) return fail(PCABI_E_ARG, "bad arguments");
+    PackLayout lay;
+    lay.out = out0;
+    for (int64_t i = 0; i < n_parts; ++i) {
+        if (parts[i].l_seq < 0 || parts[i].name_len < 0 || parts[i].name_len > kMaxName || parts[i].aux_len < 0)
+            return fail(PCABI_E_ARG, "part " + std::to_string(i) + ": lengths >= 0, a name of at most 254 bytes");
+        lay.place(&parts[i]);
+    }
+    if (tiles) *tiles = lay.tiles;
+    return lay.out;
+}
+
+int pcabi_bam_pack_dev(void *stream, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                       const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                       int64_t n_tiles, uint8_t *out, int64_t out_cap) {
+    if (seq_n < 0 || qual_n < 0 || side_n < 0 || n_parts < 0 || n_tiles < 0 || out_cap < 0 || (n_parts > 0 && !parts) ||
+        (seq_n > 0 && !seq) || (qual_n > 0 && !qual) || (side_n > 0 && !side) || (out_cap > 0 && !out))
+        return fail(PCABI_E_ARG, "bad arguments");
+    return launch_pack((hipStream_t)stream, seq, seq_n, qual, qual_n, side, side_n, parts, n_parts, n_tiles, out, out_cap);
+}
+
+int pcabi_bam_pack_host(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                        const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                        uint8_t *out, int64_t out_cap) {
+    if (seq_n < 0 || qual_n < 0 || side_n < 0 || n_parts < 0 || out_cap < 0 || (n_parts > 0 && !parts) ||
+        (seq_n > 0 && !seq) || (qual_n > 0 && !qual) || (side_n > 0 && !side) || (out_cap > 0 && !out))
+        return fail(PCABI_E_ARG, "bad arguments");
+    int64_t tiles = 0, end = 0;
+    for (int64_t i = 0; i < n_parts; ++i) {
+        const pcabi_bam_part &p = parts[i];
+        if (!part_fits(p, seq_n, qual_n, side_n, out_cap) || p.tile0 != tiles || p.out < end)
+            return fail(PCABI_E_ARG, "part " + std::to_string(i) + " of the table does not fit the buffers");
+        tiles += part_tiles(p);
+        end = p.out + part_size(p);
+    }
+    if (device < 0) {
+        for (int64_t i = 0; i < n_parts; ++i) pack_part(parts[i], seq, qual, side, out);
+        return 0;
+    }
+    BAM_TRY(hipSetDevice(device));
+    // the output sits between 64 guard bytes on the device, checked after the kernel; bytes no part
+    // owns go up and come back as they were
+    constexpr int64_t kGuard = 64;
+    const int64_t base = kGuard + (int64_t)((uintptr_t)out & 15u);   // as far off a 16-byte boundary as the caller's pointer
+    std::vector<uint8_t> stage((size_t)(base + out_cap + kGuard), 0xA5);
+    if (out_cap > 0) std::memcpy(stage.data() + base, out, (size_t)out_cap);
+    uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_side = nullptr, *d_out = nullptr;
+    pcabi_bam_part *d_parts = nullptr;
+    int rc = 0;
+    auto step = [&](hipError_t e, const char *what) {
+        if (!rc && e != hipSuccess) rc = fail(PCABI_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    auto up = [&](uint8_t **d, const void *h, int64_t n) {
+        step(hipMalloc((void **)d, (size_t)n + 64), "hipMalloc");
+        if (!rc && n > 0) step(hipMemcpy(*d, h, (size_t)n, hipMemcpyHostToDevice), "hipMemcpy");
+    };
+    up(&d_seq, seq, seq_n);
+    up(&d_qual, qual, qual_n);
+    up(&d_side, side, side_n);
+    up((uint8_t **)&d_parts, parts, n_parts * (int64_t)sizeof(pcabi_bam_part));
+    up(&d_out, stage.data(), (int64_t)stage.size());
+    if (!rc) rc = launch_pack(nullptr, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, tiles, d_out + base, out_cap);
+    if (!rc) step(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    if (!rc) step(hipMemcpy(stage.data(), d_out, stage.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+    for (int64_t g = 0; g < kGuard && !rc; ++g)
+        if (stage[(size_t)(base - 1 - g)] != 0xA5 || stage[(size_t)(base + out_cap + g)] != 0xA5)
+            rc = fail(PCABI_E_DEVICE, "k_bam_pack wrote outside its output");
+    if (!rc && out_cap > 0) std::memcpy(out, stage.data() + base, (size_t)out_cap);
+    (void)hipFree(d_seq);
+    (void)hipFree(d_qual);
+    (void)hipFree(d_side);
+    (void)hipFree(d_parts);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+void pcabi_bam_pack_last_times(int reset, double *ms, int64_t *bytes) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    harvest();
+    if (ms) *ms = g_ms[4];
+    if (bytes) *bytes = g_pack_bytes;
+    if (reset) {
+        g_ms[4] = 0;
+        g_pack_bytes = 0;
+    }
 }
 
 }  // extern "C"

@@ -731,6 +731,22 @@ int64_t pcabi_bgzf_host(int device, const uint8_t *in, int64_t n, const int64_t 
     return zn + tail;
 }
 
+int64_t pcabi_bgzf_scratch_bytes(int64_t n, int64_t block_len) {
+    if (n < 0 || block_len < 1 || block_len > kBgzfBlockCap) return fail(PCABI_E_ARG, "block_len 1..65280");
+    return scratch_bytes((n + block_len - 1) / block_len);
+}
+
+int pcabi_bgzf_dev(void *stream, const uint8_t *in, int64_t n, int64_t block_len, uint8_t *out, int64_t cap,
+                   int64_t *out_len, void *scratch, int64_t scratch_len) {
+    if (n < 0 || cap < 0 || !out_len || !scratch || (n > 0 && !in) || (cap > 0 && !out) || block_len < 1 ||
+        block_len > kBgzfBlockCap)
+        return fail(PCABI_E_ARG, "bad arguments");
+    const int64_t nb = (n + block_len - 1) / block_len;
+    if (nb > INT32_MAX) return fail(PCABI_E_ARG, "too many blocks for one call");
+    if (scratch_len < scratch_bytes(nb)) return fail(PCABI_E_ARG, "scratch smaller than pcabi_bgzf_scratch_bytes");
+    return launch((hipStream_t)stream, in, n, nullptr, nb, block_len, 1, 18, out, cap, out_len, scratch);
+}
+
 int pcabi_bgzf_write_eof(const char *path) {
     if (!path) return fail(PCABI_E_ARG, "bad arguments");
     FILE *f = std::fopen(path, "ab");

@@ -49,6 +49,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -120,6 +121,10 @@ struct BamState {
     std::vector<uint8_t> h_seq, h_qual, h_codes;   // the host path's outputs
     const uint8_t *seq = nullptr, *qual = nullptr, *codes = nullptr;
     pcabi_internal::BamDev *dev = nullptr;
+    std::string header_text;          // the input's header text (pcabi_fastx_bam_header)
+    bool keep_aux = false;            // pcabi_fastx_keep_aux: the staged records' aux bytes, copied from the window
+    std::vector<uint8_t> aux, stored;
+    std::vector<int64_t> aux_off;
 };
 
 struct pcabi_fastx {
@@ -277,6 +282,10 @@ struct pcabi_reads {
     RawVec<uint8_t> codes;                   // Dna5, 4-aligned starts, 16 B tail padding (N)
     std::vector<int64_t> code_off;
     std::vector<int32_t> len;
+    // a BAM reader with pcabi_fastx_keep_aux: the records' aux bytes and whether their bases are as stored;
+    // empty otherwise (aux_off too)
+    std::vector<uint8_t> aux, as_stored;
+    std::vector<int64_t> aux_off;
 };
 
 namespace {
@@ -1036,6 +1045,9 @@ static int bam_fill(pcabi_fastx *r) {
     s->recs.clear();
     s->names.clear();
     s->name_off.assign(1, 0);
+    s->aux.clear();
+    s->stored.clear();
+    s->aux_off.assign(1, 0);
     s->next = 0;
     Layout lay;
     while (s->recs.empty() && !s->pending) {
@@ -1050,11 +1062,12 @@ static int bam_fill(pcabi_fastx *r) {
             if (h > 0) {
                 s->header_done = true;
                 s->at = (size_t)h;
+                s->header_text.assign((const char *)s->win.data() + 8, (size_t)le32(s->win.data() + 4));
             }
         }
         if (s->header_done) {
             int64_t at = (int64_t)s->at;
-            bool invalid = false;
+            bool invalid = false, bad_aux = false;
             for (;;) {
                 pcabi_bam_rec rec;
                 int64_t size = 0;
@@ -1062,6 +1075,17 @@ static int bam_fill(pcabi_fastx *r) {
                 if (rc <= 0) {
                     invalid = rc < 0;
                     break;
+                }
+                if (s->keep_aux && !(rec.flag & kSkipFlags)) {
+                    const int64_t a0 = rec.seq_at + ((int64_t)rec.l_seq + 1) / 2 + rec.l_seq;
+                    const uint8_t *ax = s->win.data() + at + a0;
+                    if (!aux_walks(ax, size - a0)) {
+                        bad_aux = true;
+                        break;
+                    }
+                    s->aux.insert(s->aux.end(), ax, ax + (size - a0));
+                    s->aux_off.push_back((int64_t)s->aux.size());
+                    s->stored.push_back((rec.flag & kReverse) ? 0 : 1);
                 }
                 at += size;
                 if (rec.flag & kSkipFlags) continue;
@@ -1073,6 +1097,7 @@ static int bam_fill(pcabi_fastx *r) {
             }
             s->at = (size_t)at;
             if (invalid) bam_fault(s, "invalid BAM record at offset " + std::to_string(s->base + at));
+            if (bad_aux) bam_fault(s, "invalid aux tags in the BAM record at offset " + std::to_string(s->base + at));
         }
         if (!s->recs.empty() || s->pending) break;
         // nothing whole in the window: more bytes behind the carried ones, or the end
@@ -1161,6 +1186,14 @@ static int64_t bam_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, pc
             b->code_off.push_back(code_base + (q.code_out - c0));
             b->len.push_back(q.l_seq);
         }
+        if (s->keep_aux) {
+            if (b->aux_off.empty()) b->aux_off.push_back(0);
+            b->aux.insert(b->aux.end(), s->aux.begin() + s->aux_off[i], s->aux.begin() + s->aux_off[j]);
+            for (size_t k = i; k < j; ++k) {
+                b->aux_off.push_back(b->aux_off.back() + (s->aux_off[k + 1] - s->aux_off[k]));
+                b->as_stored.push_back(s->stored[k]);
+            }
+        }
         b->n += (int64_t)(j - i);
         s->next = j;
     }
@@ -1246,6 +1279,28 @@ void pcabi_encode_dna5_gather(const uint64_t *src, const int64_t *len, const int
     for (int k = 0; k < nt; ++k)
         if (cut[k] < cut[k + 1]) th.emplace_back(run, cut[k], cut[k + 1]);
     for (auto &t : th) t.join();
+}
+
+int pcabi_fastx_keep_aux(pcabi_fastx *r, int on) {
+    if (!r) return fail(PCABI_E_ARG, "bad arguments");
+    if (r->bam) r->bam->keep_aux = on != 0;
+    return 0;
+}
+
+int pcabi_fastx_bam_header(const pcabi_fastx *r, const char **text, int64_t *len) {
+    if (!r || !text || !len) return fail(PCABI_E_ARG, "bad arguments");
+    *text = r->bam ? r->bam->header_text.data() : "";
+    *len = r->bam ? (int64_t)r->bam->header_text.size() : 0;
+    return 0;
+}
+
+int pcabi_reads_aux(const pcabi_reads *b, const uint8_t **aux, const int64_t **aux_off, const uint8_t **as_stored) {
+    if (!b || !aux || !aux_off || !as_stored) return fail(PCABI_E_ARG, "bad arguments");
+    const bool have = !b->aux_off.empty();
+    *aux = have ? b->aux.data() : nullptr;
+    *aux_off = have ? b->aux_off.data() : nullptr;
+    *as_stored = have ? b->as_stored.data() : nullptr;
+    return 0;
 }
 
 int64_t pcabi_reads_count(const pcabi_reads *b) { return b ? b->n : 0; }
@@ -1434,6 +1489,79 @@ void put_record(S &o, bool fasta, const char *name, size_t nn, bool own, const c
     }
 }
 
+// What a writer is asked for (pcabi_reads_write's arguments), and the part enumeration the text writers
+// and the BAM writer share: part(name, name_len, own, s0, ns, q0, nq) is called for every record read i
+// gives, in output order -- name: the batch's own header bytes (stable) or a numbered copy (own = true);
+// [s0, s0 + ns) of the read's sequence, [q0, q0 + nq) of its qualities. Returns whether the read
+// produced any output (the reference counts a read into its bin only then, porechop_abi.py:598-604).
+struct WriteArgs {
+    const pcabi_reads *b;
+    const int32_t *start_trim, *end_trim;
+    const int64_t *cut_off, *cuts;
+    int min_split_read_size, discard_middle, untrimmed;
+    const uint8_t *select;
+};
+
+template <class F>
+bool read_parts(const WriteArgs &w, int64_t i, std::vector<std::pair<int64_t, int64_t>> &rg, F &&part) {
+    const pcabi_reads *b = w.b;
+    const int64_t *cut_off = w.cut_off, *cuts = w.cuts;
+    if (w.select && !w.select[i]) return false;
+    const char *name = b->names.data() + b->name_off[i];
+    const size_t nn = (size_t)(b->name_off[i + 1] - b->name_off[i]);
+    const int64_t ns = b->seq_off[i + 1] - b->seq_off[i];
+    const int64_t nq = b->qual_off[i + 1] - b->qual_off[i];
+    const int64_t st = w.start_trim ? w.start_trim[i] : 0, et = w.end_trim ? w.end_trim[i] : 0;
+    // get_seq_with_start_end_adapters_trimmed / get_quals_... (nanopore_read.py:66-82)
+    int64_t sa = 0, sb = ns, qa = 0, qb = nq;
+    if (st || et) {
+        py_slice(ns, st, ns - et, &sa, &sb);
+        py_slice(nq, st, nq - et, &qa, &qb);
+    }
+    bool split = false;
+    if (cut_off)
+        for (int64_t k = cut_off[i]; k < cut_off[i + 1] && !split; ++k) split = cuts[2 * k + 1] > cuts[2 * k];
+    if (!split) {
+        if (w.untrimmed) { sa = 0; sb = ns; qa = 0; qb = nq; }
+        if (sb == sa) return false;   // no empty sequences
+        part(name, nn, false, sa, sb - sa, qa, qb - qa);
+        return true;
+    }
+    if (w.discard_middle) return false;
+    // split parts (get_split_read_parts, nanopore_read.py:84-104): positions of the trimmed
+    // sequence inside any cut range are dropped
+    rg.clear();
+    for (int64_t k = cut_off[i]; k < cut_off[i + 1]; ++k)
+        if (cuts[2 * k + 1] > cuts[2 * k]) rg.emplace_back(cuts[2 * k], cuts[2 * k + 1]);
+    std::sort(rg.begin(), rg.end());
+    const int64_t tl = sb - sa;
+    int n_part = 0;
+    size_t ri = 0;
+    int64_t run = 0;   // start of the current kept run
+    auto emit = [&](int64_t a, int64_t e) {
+        if (e - a <= 0 || e - a < w.min_split_read_size) return;
+        ++n_part;
+        const std::string nm = numbered(name, nn, n_part);
+        part(nm.data(), nm.size(), true, sa + a, e - a, qa + a, e - a);
+    };
+    int64_t pos = 0;
+    while (pos < tl) {
+        while (ri < rg.size() && rg[ri].second <= pos) ++ri;
+        if (ri < rg.size() && rg[ri].first <= pos) {   // pos is cut
+            emit(run, pos);
+            int64_t e = rg[ri].second;
+            for (size_t rj = ri; rj < rg.size() && rg[rj].first <= e; ++rj) e = std::max(e, rg[rj].second);
+            pos = std::min(e, tl);
+            run = pos;
+        } else {
+            const int64_t nxt = ri < rg.size() ? std::min(rg[ri].first, tl) : tl;
+            pos = nxt;
+        }
+    }
+    emit(run, tl);
+    return n_part > 0;
+}
+
 }  // namespace
 
 // seconds the calling thread's last pcabi_reads_write* spent laying the records out (sizing, fill,
@@ -1460,67 +1588,13 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
         o.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
         if (o.fd < 0) return fail(PCABI_E_ARG, std::string("could not write ") + path);
     }
-    // returns whether the read produced any output (the reference counts a read into its bin only
-    // then, porechop_abi.py:598-604)
+    const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
     auto format = [&](int64_t i, auto &o, std::vector<std::pair<int64_t, int64_t>> &rg) -> bool {
-        if (select && !select[i]) return false;
-        const char *name = b->names.data() + b->name_off[i];
-        const size_t nn = (size_t)(b->name_off[i + 1] - b->name_off[i]);
-        const char *seq = b->seq.data() + b->seq_off[i];
-        const int64_t ns = b->seq_off[i + 1] - b->seq_off[i];
-        const char *qual = b->qual.data() + b->qual_off[i];
-        const int64_t nq = b->qual_off[i + 1] - b->qual_off[i];
+        const char *seq = b->seq.data() + b->seq_off[i], *qual = b->qual.data() + b->qual_off[i];
         const bool rna = b->rna[i] != 0;
-        const int64_t st = start_trim ? start_trim[i] : 0, et = end_trim ? end_trim[i] : 0;
-        // get_seq_with_start_end_adapters_trimmed / get_quals_... (nanopore_read.py:66-82)
-        int64_t sa = 0, sb = ns, qa = 0, qb = nq;
-        if (st || et) {
-            py_slice(ns, st, ns - et, &sa, &sb);
-            py_slice(nq, st, nq - et, &qa, &qb);
-        }
-        bool split = false;
-        if (cut_off)
-            for (int64_t k = cut_off[i]; k < cut_off[i + 1] && !split; ++k) split = cuts[2 * k + 1] > cuts[2 * k];
-        if (!split) {
-            if (untrimmed) { sa = 0; sb = ns; qa = 0; qb = nq; }
-            if (sb == sa) return false;   // no empty sequences
-            put_record(o, fasta != 0, name, nn, false, seq + sa, (size_t)(sb - sa), qual + qa, (size_t)(qb - qa), rna);
-            return true;
-        }
-        if (discard_middle) return false;
-        // split parts (get_split_read_parts, nanopore_read.py:84-104): positions of the trimmed
-        // sequence inside any cut range are dropped
-        rg.clear();
-        for (int64_t k = cut_off[i]; k < cut_off[i + 1]; ++k)
-            if (cuts[2 * k + 1] > cuts[2 * k]) rg.emplace_back(cuts[2 * k], cuts[2 * k + 1]);
-        std::sort(rg.begin(), rg.end());
-        const int64_t tl = sb - sa;
-        int part = 0;
-        size_t ri = 0;
-        int64_t run = 0;   // start of the current kept run
-        auto emit = [&](int64_t a, int64_t e) {
-            if (e - a <= 0 || e - a < min_split_read_size) return;
-            ++part;
-            const std::string nm = numbered(name, nn, part);
-            put_record(o, fasta != 0, nm.data(), nm.size(), true, seq + sa + a, (size_t)(e - a), qual + qa + a,
-                       (size_t)(e - a), rna);
-        };
-        int64_t pos = 0;
-        while (pos < tl) {
-            while (ri < rg.size() && rg[ri].second <= pos) ++ri;
-            if (ri < rg.size() && rg[ri].first <= pos) {   // pos is cut
-                emit(run, pos);
-                int64_t e = rg[ri].second;
-                for (size_t rj = ri; rj < rg.size() && rg[rj].first <= e; ++rj) e = std::max(e, rg[rj].second);
-                pos = std::min(e, tl);
-                run = pos;
-            } else {
-                const int64_t nxt = ri < rg.size() ? std::min(rg[ri].first, tl) : tl;
-                pos = nxt;
-            }
-        }
-        emit(run, tl);
-        return part > 0;
+        return read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+            put_record(o, fasta != 0, name, nn, own, seq + s0, (size_t)ns, qual + q0, (size_t)nq, rna);
+        });
     };
     // One stream: the page-cache copy is the cost, and writers of one file serialise on its
     // inode (measured: threads writing disjoint ranges with pwritev were no faster). r05: a plain
@@ -1640,6 +1714,215 @@ extern "C" void pcabi_reads_write_last_times(double *layout, double *compress, d
     if (layout) *layout = g_write_times[0];
     if (compress) *compress = g_write_times[1];
     if (write) *write = g_write_times[2];
+}
+
+// ---- BAM writer ------------------------------------------------------------------------------
+namespace pcabi_internal {
+// the device half (csrc/pcabi_bam.hip): the stream packed and compressed on the device; sink receives its
+// members (pinned memory, valid inside the call)
+int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
+                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink);
+}
+
+namespace {
+
+// One BGZF member of data[0, n) (n <= 65280) appended to z: zlib raw deflate, stored when that fails to fit.
+bool bgzf_member(const uint8_t *data, size_t n, std::vector<uint8_t> &z) {
+    uint8_t body[PCABI_BGZF_MEMBER_MAX];
+    size_t zn = 0;
+    for (int level : {Z_DEFAULT_COMPRESSION, 0}) {
+        z_stream zs;
+        std::memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        zs.next_in = const_cast<Bytef *>(data);
+        zs.avail_in = (uInt)n;
+        zs.next_out = body;
+        zs.avail_out = (uInt)(PCABI_BGZF_MEMBER_MAX - 26);
+        const int rc = deflate(&zs, Z_FINISH);
+        zn = zs.total_out;
+        deflateEnd(&zs);
+        if (rc == Z_STREAM_END) break;
+        if (level == 0) return false;
+    }
+    const uint32_t bsize = (uint32_t)(zn + 26 - 1), crc = (uint32_t)crc32(crc32(0, nullptr, 0), data, (uInt)n), isize = (uint32_t)n;
+    const uint8_t hdr[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8)};
+    z.insert(z.end(), hdr, hdr + 18);
+    z.insert(z.end(), body, body + zn);
+    for (uint32_t v : {crc, isize})
+        for (int k = 0; k < 4; ++k) z.push_back((uint8_t)(v >> (8 * k)));
+    return true;
+}
+
+}  // namespace
+
+extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
+                                     const int32_t *end_trim, const int64_t *cut_off, const int64_t *cuts,
+                                     int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
+                                     const char *header_text, int64_t header_len, int keep_aux, int device) {
+    using namespace pcabi_bam;
+    if (!b || !path || header_len < 0 || header_len > INT32_MAX - 16 || (header_len > 0 && !header_text))
+        return fail(PCABI_E_ARG, "bad arguments");
+    if (std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "BAM output goes to files, not stdout");
+    g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
+    const double t_begin = wall_s();
+    const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
+    const bool have_aux = keep_aux && !b->aux_off.empty();
+    const bool no_qual = b->type == PCABI_FASTA;
+    // the parts and their side blob (name, then aux bytes), per thread's range of reads, then joined
+    const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
+    std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
+    std::vector<std::vector<uint8_t>> t_side((size_t)nt);
+    std::vector<int64_t> t_emit((size_t)nt, 0);
+    auto par = [&](auto &&fn) {
+        if (nt <= 1) {
+            fn(0);
+            return;
+        }
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t) th.emplace_back(fn, t);
+        for (auto &x : th) x.join();
+    };
+    par([&](int t) {
+        std::vector<std::pair<int64_t, int64_t>> rg;
+        std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
+        std::vector<uint8_t> &side = t_side[(size_t)t];
+        for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
+            const int64_t ns_all = b->seq_off[i + 1] - b->seq_off[i];
+            t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+                pcabi_bam_part p;
+                std::memset(&p, 0, sizeof p);
+                p.seq_src = b->seq_off[i] + s0;
+                p.qual_src = (no_qual || nq < ns) ? -1 : b->qual_off[i] + q0;
+                p.side_off = (int64_t)side.size();
+                p.l_seq = (int32_t)ns;
+                // the name: the header up to its first space or tab, at most 254 bytes, "*" when empty
+                size_t k = 0;
+                while (k < nn && k < (size_t)kMaxName && name[k] != ' ' && name[k] != '\t') ++k;
+                if (k == 0) side.push_back('*'), k = 1;
+                else side.insert(side.end(), name, name + k);
+                p.name_len = (int32_t)k;
+                if (have_aux) {
+                    const uint8_t *ax = b->aux.data() + b->aux_off[i];
+                    const int64_t an = b->aux_off[i + 1] - b->aux_off[i];
+                    if (!own && s0 == 0 && ns == ns_all && b->as_stored[i]) {
+                        side.insert(side.end(), ax, ax + an);   // the whole read, as stored: verbatim
+                    } else {   // a changed read: without the tags that count its bases
+                        for (int64_t at = 0; at < an;) {
+                            const int64_t nx = aux_next(ax, an, at);
+                            if (nx < 0) break;
+                            if (!aux_positional(ax + at)) side.insert(side.end(), ax + at, ax + nx);
+                            at = nx;
+                        }
+                    }
+                    p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
+                }
+                parts.push_back(p);
+            }) ? 1 : 0;
+        }
+    });
+    std::vector<pcabi_bam_part> parts;
+    std::vector<uint8_t> side;
+    int64_t emitted = 0;
+    for (int t = 0; t < nt; ++t) {
+        const int64_t base = (int64_t)side.size();
+        for (pcabi_bam_part p : t_parts[(size_t)t]) {
+            p.side_off += base;
+            parts.push_back(p);
+        }
+        side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
+        emitted += t_emit[(size_t)t];
+    }
+    std::vector<uint8_t> head;
+    if (!append) {
+        static const char kDefault[] = "@HD\tVN:1.6\tSO:unknown\n";
+        const char *text = header_text ? header_text : kDefault;
+        const int64_t tn = header_text ? header_len : (int64_t)sizeof kDefault - 1;
+        const uint8_t magic[8] = {'B', 'A', 'M', 1, (uint8_t)tn, (uint8_t)(tn >> 8), (uint8_t)(tn >> 16), (uint8_t)(tn >> 24)};
+        head.insert(head.end(), magic, magic + 8);
+        head.insert(head.end(), text, text + tn);
+        head.insert(head.end(), 4, 0);   // n_ref = 0
+    }
+    PackLayout lay;
+    lay.out = (int64_t)head.size();
+    for (pcabi_bam_part &p : parts) lay.place(&p);
+    const int64_t stream_n = lay.out;
+    const int64_t seq_n = (int64_t)b->seq.size(), qual_n = (int64_t)b->qual.size();
+    // the file: opened before anything is compressed, written in large write() calls
+    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
+    if (fd < 0) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+    bool ok = true;
+    auto write_all = [&](const uint8_t *p, int64_t n) {
+        const double t1 = wall_s();
+        for (size_t k = 0; ok && k < (size_t)n;) {
+            const ssize_t w = ::write(fd, p + k, std::min<size_t>((size_t)n - k, 256u << 20));
+            if (w < 0) {
+                if (errno == EINTR) continue;
+                ok = false;
+                break;
+            }
+            k += (size_t)w;
+        }
+        g_write_times[2] += wall_s() - t1;
+    };
+    if (device >= 0) {
+        g_write_times[0] = wall_s() - t_begin;
+        const double t0 = wall_s();
+        if (stream_n > 0) {
+            const int64_t zn = pcabi_internal::bam_write_dev(device, head.data(), (int64_t)head.size(), (const uint8_t *)b->seq.data(),
+                                                             seq_n, (const uint8_t *)b->qual.data(), qual_n, side.data(),
+                                                             (int64_t)side.size(), parts.data(), (int64_t)parts.size(), lay.tiles,
+                                                             stream_n, write_all);
+            if (zn < 0) {
+                ::close(fd);
+                return (int)zn;
+            }
+        }
+        g_write_times[1] = wall_s() - t0 - g_write_times[2];
+    } else {
+        std::vector<uint8_t, NoInit<uint8_t>> stream;
+        stream.resize((size_t)stream_n);
+        if (!head.empty()) std::memcpy(stream.data(), head.data(), head.size());
+        const int64_t np = (int64_t)parts.size();
+        const int pt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, stream_n >> 20));
+        std::atomic<int64_t> next{0};
+        auto pool = [&](int threads, auto &&fn) {
+            if (threads <= 1) {
+                fn();
+                return;
+            }
+            std::vector<std::thread> th;
+            for (int t = 0; t < threads; ++t) th.emplace_back(fn);
+            for (auto &x : th) x.join();
+        };
+        pool(pt, [&] {
+            for (int64_t i0; (i0 = next.fetch_add(256)) < np;)
+                for (int64_t i = i0; i < std::min(np, i0 + 256); ++i)
+                    pack_part(parts[(size_t)i], (const uint8_t *)b->seq.data(), (const uint8_t *)b->qual.data(), side.data(),
+                              stream.data());
+        });
+        g_write_times[0] = wall_s() - t_begin;
+        const double t0 = wall_s();
+        const int64_t block = PCABI_BGZF_BLOCK_CAP, nm = (stream_n + block - 1) / block;
+        const int zt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, nm / 4));
+        std::vector<std::vector<uint8_t>> zs((size_t)zt);
+        std::atomic<bool> zok{true};
+        std::atomic<int> slot{0};
+        pool(zt, [&] {
+            const int t = slot.fetch_add(1);
+            for (int64_t m = nm * t / zt; m < nm * (t + 1) / zt; ++m)
+                if (!bgzf_member(stream.data() + m * block, (size_t)std::min(block, stream_n - m * block), zs[(size_t)t])) zok = false;
+        });
+        g_write_times[1] = wall_s() - t0;
+        if (!zok) {
+            ::close(fd);
+            return fail(PCABI_E_ARG, "zlib failed on a BGZF member");
+        }
+        for (const auto &v : zs) write_all(v.data(), (int64_t)v.size());
+    }
+    ok = (::close(fd) == 0) && ok;
+    if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
+    return (int)std::min<int64_t>(emitted, INT32_MAX);
 }
 
 extern "C" int64_t pcabi_gzip_plan_lines(const char *text, int64_t n, int64_t long_line, int64_t cap,

@@ -792,3 +792,39 @@ def bam_unpack(data, recs, totals=None, device=0, out=None):
                                      _ptr(qual), qual.size, _ptr(codes), codes.size, int(totals[2]) - 16)
     check(int(rc), 'pcabi_bam_unpack_host')
     return seq, qual, codes
+
+
+# ---- unaligned BAM output (csrc/pcabi_bam.h, csrc/pcabi_bam.hip) ---------------------------------
+# include/pcabi.h pcabi_bam_part
+BAM_PART = np.dtype([('seq_src', np.int64), ('qual_src', np.int64), ('side_off', np.int64), ('out', np.int64),
+                     ('tile0', np.int64), ('l_seq', np.int32), ('name_len', np.int32), ('aux_len', np.int32),
+                     ('reserved', np.int32)])
+
+
+def bam_pack_plan(parts, out0=0):
+    """Output offsets and tiles of a part table (pcabi_bam_pack_plan): fills parts['out'] and
+    parts['tile0'] in place for a record chain that starts at out0; returns (the chain's end, tiles).
+    parts: a C-contiguous BAM_PART array with the sources, the side offsets and the lengths set."""
+    if parts.dtype != BAM_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('bam_pack_plan: parts is a C-contiguous BAM_PART array')
+    tiles = np.zeros(1, np.int64)
+    end = lib().pcabi_bam_pack_plan(_ptr(parts), parts.size, int(out0), _ptr(tiles))
+    if end < 0:
+        check(int(end), 'pcabi_bam_pack_plan')
+    return int(end), int(tiles[0])
+
+
+def bam_pack(seq, qual, side, parts, out, device=0):
+    """The parts of a planned table laid out as BAM records in `out` (pcabi_bam_pack_host): on GPU
+    `device`, or with the host build of the same code when device < 0. seq / qual: the letters and the
+    quality characters the parts' sources index; side: the names and aux bytes; out: a C-contiguous
+    uint8 array, filled in place (bytes no part owns keep their values) and returned."""
+    arrs = [np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, np.uint8)
+            for a in (seq, qual, side)]
+    parts = np.ascontiguousarray(parts, BAM_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('bam_pack: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_bam_pack_host(int(device), _ptr(arrs[0]), arrs[0].size, _ptr(arrs[1]), arrs[1].size, _ptr(arrs[2]),
+                                   arrs[2].size, _ptr(parts), parts.size, _ptr(out), out.size)
+    check(int(rc), 'pcabi_bam_pack_host')
+    return out

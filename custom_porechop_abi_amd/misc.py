@@ -51,6 +51,11 @@ def _declare(L):
         'pcabi_reads_write_dev': ([P, ctypes.c_char_p, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P, c_int],
                                   c_int),
         'pcabi_bgzf_write_eof': ([ctypes.c_char_p], c_int),
+        'pcabi_reads_write_bam': ([P, ctypes.c_char_p, c_int, P, P, P, P, c_int, c_int, c_int, P, ctypes.c_char_p, i64,
+                                   c_int, c_int], c_int),
+        'pcabi_fastx_keep_aux': ([P, c_int], c_int),
+        'pcabi_reads_aux': ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)], c_int),
+        'pcabi_fastx_bam_header': ([P, ctypes.POINTER(P), ctypes.POINTER(i64)], c_int),
         'pcabi_fastx_record_start': ([P, i64], i64),
         'pcabi_fastx_set_range': ([P, i64, i64], c_int),
         'pcabi_fastx_remaining': ([P], i64),
@@ -94,9 +99,13 @@ class ReadBatch(object):
     names / seq / qual: uint8 buffers with int64 offsets [n + 1]; rna: uint8 [n];
     codes: Dna5 uint8 buffer, code_off int64 [n] (4-aligned), lengths int32 [n] -- the layout
     engine.SeqPack builds, so (codes, code_off + start, length) are engine windows directly.
-    The native batch lives as long as this object or any of its arrays (write_reads uses it)."""
+    The native batch lives as long as this object or any of its arrays (write_reads uses it).
+    bam_header: the header text (bytes) of the BAM file the batch came from, else None. With
+    keep_aux (read_batches / load_batch) a BAM batch also holds its records' aux tags: aux_bytes /
+    aux_off int64 [n + 1] and as_stored uint8 [n] (0: a reverse-strand record, whose bases the reader
+    reverse-complemented); all None otherwise."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, bam_header=None):
         L = _declare(lib())
         v = _View()
         self._owner = _Owner(handle)
@@ -117,6 +126,14 @@ class ReadBatch(object):
         self.codes = _view(o, v.codes, np.uint8, int(v.codes_len))
         self.code_off = _view(o, v.code_off, np.int64, n)
         self.lengths = _view(o, v.len, np.int32, n)
+        self.bam_header = bam_header
+        ax, ao, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(L.pcabi_reads_aux(handle, ctypes.byref(ax), ctypes.byref(ao), ctypes.byref(st)), 'pcabi_reads_aux')
+        self.aux_bytes = self.aux_off = self.as_stored = None
+        if ao.value:
+            self.aux_off = _view(o, ao.value, np.int64, n + 1)
+            self.aux_bytes = _view(o, ax.value, np.uint8, int(self.aux_off[-1]))
+            self.as_stored = _view(o, st.value, np.uint8, n)
 
     @property
     def _h(self):
@@ -136,6 +153,12 @@ class ReadBatch(object):
 
     def quals(self, i):
         return self._text(self.qual, self.qual_off, i)
+
+    def aux(self, i):
+        """Record i's aux tags as the file holds them (bytes); None when the batch keeps none."""
+        if self.aux_off is None:
+            return None
+        return self.aux_bytes[self.aux_off[i]:self.aux_off[i + 1]].tobytes()
 
     def spacer_line(self, i):
         return self._text(self.spacer, self.spacer_off, i)
@@ -256,13 +279,25 @@ def is_bam(path):
         return False
 
 
-def _fastx_open(L, path, raw, gunzip_device):
+def _fastx_open(L, path, raw, gunzip_device, keep_aux=False):
     """pcabi_fastx_open, or pcabi_fastx_open_dev when gunzip_device names a GPU (a block-gzipped file
-    is then inflated there; any other file reads as before). Returns (rc, handle)."""
+    is then inflated there; any other file reads as before). keep_aux: pcabi_fastx_keep_aux. Returns
+    (rc, handle)."""
     h = ctypes.c_void_p()
     if gunzip_device is None:
-        return L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h)), h
-    return L.pcabi_fastx_open_dev(os.fsencode(path), int(raw), int(gunzip_device), ctypes.byref(h)), h
+        rc = L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h))
+    else:
+        rc = L.pcabi_fastx_open_dev(os.fsencode(path), int(raw), int(gunzip_device), ctypes.byref(h))
+    if rc == 0 and keep_aux:
+        L.pcabi_fastx_keep_aux(h, 1)
+    return rc, h
+
+
+def _bam_header(L, h):
+    """A BAM reader's header text (bytes) once it has read a batch; None for any other input."""
+    p, n = ctypes.c_void_p(), ctypes.c_int64()
+    L.pcabi_fastx_bam_header(h, ctypes.byref(p), ctypes.byref(n))
+    return ctypes.string_at(p.value, n.value) if n.value > 0 else None
 
 
 def ramp_sizes(max_reads, remaining_reads=None, done=0):
@@ -279,7 +314,7 @@ def ramp_sizes(max_reads, remaining_reads=None, done=0):
 
 
 def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_range=None, first_reads=None,
-                 ramp=False, gunzip_device=None):
+                 ramp=False, gunzip_device=None, keep_aux=False):
     """Stream a FASTA / FASTQ(.gz) or unaligned BAM file as ReadBatch objects (pcabi_fastx_next; a BAM
     file's records arrive as FASTQ batches, see include/pcabi.h "unaligned BAM input"); byte_range =
     (begin, end) record starts of a plain file (record_boundaries) reads only that range;
@@ -288,9 +323,11 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
     batches shrink too, from the bytes left and the bytes per read so far). Batching never changes
     what is read or written, only when. gunzip_device: a GPU that inflates a block-gzipped (BGZF)
     input (pcabi_fastx_open_dev) and, for a BAM file, unpacks its records; None reads every gzip
-    input with zlib."""
+    input with zlib. keep_aux: a BAM input's batches keep their records' aux tags (ReadBatch.aux),
+    for write_reads(..., 'bam', keep_aux=True); any other input: no effect. A BAM input's batches
+    carry its header text (ReadBatch.bam_header)."""
     L = _declare(lib())
-    rc, h = _fastx_open(L, path, raw, gunzip_device)
+    rc, h = _fastx_open(L, path, raw, gunzip_device, keep_aux)
     if rc != 0:
         raise ValueError(_open_error(path))
     if byte_range is not None and L.pcabi_fastx_set_range(h, int(byte_range[0]), int(byte_range[1])) != 0:
@@ -318,7 +355,7 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
                     b_done = left0 - left
                     est = int(left * n_done / max(1, b_done))
                 want = ramp_sizes(int(max_reads), est, k)
-            yield ReadBatch(b)
+            yield ReadBatch(b, _bam_header(L, h))
     finally:
         L.pcabi_fastx_close(h)
 
@@ -346,14 +383,15 @@ def text_chunks(path, chunk_bytes, gunzip_device=None):
         L.pcabi_fastx_close(h)
 
 
-def load_batch(path, raw=False, gunzip_device=None):
+def load_batch(path, raw=False, gunzip_device=None, keep_aux=False):
     """The whole FASTA, FASTQ or BAM file as one ReadBatch (pcabi_fastx_load); raw keeps the file's
     own text. gunzip_device: a GPU that inflates a block-gzipped (BGZF) input, a BAM file included,
-    whose records are then unpacked there too (pcabi_fastx_open_dev)."""
+    whose records are then unpacked there too (pcabi_fastx_open_dev). keep_aux: as in read_batches."""
     L = _declare(lib())
     b = ctypes.c_void_p()
-    if gunzip_device is not None and _starts_bgzf(path):
-        rc, h = _fastx_open(L, path, raw, gunzip_device)
+    bam = is_bam(path)
+    if bam or (gunzip_device is not None and _starts_bgzf(path)):
+        rc, h = _fastx_open(L, path, raw, gunzip_device if _starts_bgzf(path) else None, keep_aux)
         if rc != 0:
             raise ValueError(_open_error(path))
         try:
@@ -368,9 +406,10 @@ def load_batch(path, raw=False, gunzip_device=None):
             else:
                 L.pcabi_reads_free(b)
                 raise ValueError(_open_error(path))
+            header = _bam_header(L, h)
         finally:
             L.pcabi_fastx_close(h)
-        return ReadBatch(b)
+        return ReadBatch(b, header)
     rc = L.pcabi_fastx_load(os.fsencode(path), int(raw), ctypes.byref(b))
     if rc != 0:
         raise ValueError(_open_error(path))
@@ -488,7 +527,7 @@ def get_albacore_barcode_from_path(albacore_path):
 
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
-                cut_arrays=None, gzip_device=None, bgzf=False):
+                cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
     gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
@@ -496,6 +535,15 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     gzip_device): gz = 3, one indexed BGZF member per block of at most 65280 bytes, which bgzip,
     htslib and this project's device reader take member by member; the end-of-file marker is not
     written, so batches can be appended: bgzf_finish(path) closes the file.
+    out_format 'bam' (pcabi_reads_write_bam): unaligned BAM records in BGZF members of 65280 bytes,
+    packed and compressed on GPU gzip_device, or on the host (zlib) when it is None; both give the same
+    decoded bytes. A first write (append=False) starts with the BAM header, whose text is bam_header
+    (bytes; None: '@HD\tVN:1.6\tSO:unknown\n'); bgzf_finish(path) closes the file. A record's name is
+    the header up to its first space or tab (header comments are dropped), RNA reads are written with
+    T, a FASTA batch has absent qualities, a quality-less FASTQ record's '+' padding is Phred 10.
+    keep_aux: write the aux tags a batch read with keep_aux holds -- verbatim for a read written whole
+    and as stored, without the position-dependent tags MM ML MN Mm Ml mv (dropped, not recomputed) for
+    a trimmed read, a split piece or a read from a reverse-strand record.
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -524,6 +572,15 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
     if bgzf and not (gz and gzip_device is not None):
         raise ValueError("bgzf applies to a '.gz' format compressed on a device (gzip_device)")
+    if out_format == 'bam':
+        hdr = None if bam_header is None else bytes(bam_header)
+        rc = L.pcabi_reads_write_bam(batch._h, os.fsencode(path), int(append), p(st), p(et), p(co), p(cu),
+                                     int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel), hdr,
+                                     0 if hdr is None else len(hdr), int(bool(keep_aux)),
+                                     -1 if gzip_device is None else int(gzip_device))
+        if rc < 0:
+            check(rc, 'pcabi_reads_write_bam')
+        return int(rc)
     if gz and gzip_device is not None:
         rc = L.pcabi_reads_write_dev(batch._h, os.fsencode(path), int(append), 3 if bgzf else 2, int(fasta), p(st), p(et), p(co),
                                      p(cu), int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel),
@@ -536,9 +593,23 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     return int(rc)
 
 
+def write_bam_header(path, bam_header=None):
+    """A BAM file that holds its header and no record (what write_reads(..., 'bam') starts a file
+    with), for an input without reads: one BGZF member, made here with zlib. bgzf_finish closes it."""
+    import struct
+    import zlib
+    text = b'@HD\tVN:1.6\tSO:unknown\n' if bam_header is None else bytes(bam_header)
+    data = b'BAM\1' + struct.pack('<i', len(text)) + text + struct.pack('<i', 0)
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    body = c.compress(data) + c.flush()
+    with open(path, 'wb') as f:
+        f.write(b'\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0' + struct.pack('<H', len(body) + 25) + body +
+                struct.pack('<II', zlib.crc32(data), len(data)))
+
+
 def bgzf_finish(path):
-    """Append the 28-byte BGZF end-of-file marker to a file written with write_reads(bgzf=True)
-    (pcabi_bgzf_write_eof)."""
+    """Append the 28-byte BGZF end-of-file marker to a file written with write_reads(bgzf=True) or
+    write_reads(out_format='bam') (pcabi_bgzf_write_eof)."""
     L = _declare(lib())
     check(L.pcabi_bgzf_write_eof(os.fsencode(path)), 'pcabi_bgzf_write_eof')
 

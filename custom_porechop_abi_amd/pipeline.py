@@ -36,6 +36,19 @@ def _bgzf_mode(trimmer, out_format):
         getattr(trimmer, 'gzip_device', None) is not None
 
 
+def _finish_mode(trimmer, out_format):
+    """Whether the files of this run end with the BGZF end-of-file marker: BGZF text, or BAM."""
+    return out_format == 'bam' or _bgzf_mode(trimmer, out_format)
+
+
+def _bam_kw(trimmer, out_format, b):
+    """misc.write_reads' BAM arguments for batch b: the input's header text when it was BAM, and the
+    trimmer's keep_tags."""
+    if out_format != 'bam':
+        return {}
+    return {'bam_header': getattr(b, 'bam_header', None), 'keep_aux': bool(getattr(trimmer, 'keep_tags', False))}
+
+
 class FileTrimmer(object):
     """Device state for trimming batches against one list of matching adapter sets.
 
@@ -48,14 +61,19 @@ class FileTrimmer(object):
     gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
     bgzf = False                          # device-compressed '.gz' output as plain multi-member gzip
     gunzip_device = None                  # gzip inputs through zlib on the host (set by __init__)
+    keep_tags = False                     # BAM to BAM: aux tags are dropped (set by __init__)
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
                  extra_middle_trim_bad_side=100, min_split_read_size=1000, no_split=False, discard_middle=False,
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
-                 discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False):
+                 discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False):
         self.L = L = lib()
+        # out_format 'bam' from a BAM input: the records' aux tags are read and written (misc.write_reads
+        # keep_aux: verbatim on reads written whole and as stored, without the position-dependent tags
+        # MM ML MN Mm Ml mv, which are dropped and not recomputed, on changed reads)
+        self.keep_tags = bool(keep_tags)
         self.device = int(device)
         # '.gz' output formats: zlib on the host (default) or the device encoder (misc.write_reads)
         self.gzip_device = self.device if gzip_on_device else None
@@ -298,7 +316,8 @@ class FileTrimmer(object):
                 # batch sizes ramp up at the start and down at the end (misc.ramp_sizes): the first
                 # parse and the last write are small, so they overlap the other stages
                 for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True,
-                                           gunzip_device=getattr(self, 'gunzip_device', None)):
+                                           gunzip_device=getattr(self, 'gunzip_device', None),
+                                           keep_aux=out_format == 'bam' and bool(getattr(self, 'keep_tags', False))):
                     yield b, alb
 
         def produce():
@@ -344,7 +363,7 @@ class FileTrimmer(object):
                         misc.write_reads(b, out_path, out_format, st, et, None, self.min_split, self.discard_middle,
                                          select=keep, append=not first, cut_arrays=(co, cu),
                                          gzip_device=getattr(self, 'gzip_device', None),
-                                         bgzf=_bgzf_mode(self, out_format))
+                                         bgzf=_bgzf_mode(self, out_format), **_bam_kw(self, out_format, b))
                         if segments is not None:
                             segments.append((k, at, os.path.getsize(out_path)))
                 except BaseException as ex:
@@ -357,7 +376,10 @@ class FileTrimmer(object):
                 if trace is not None:
                     trace.append(('write', k, t0, t1))
             if first and not errors and self.barcode_dir is None:   # empty input: still create the output
-                open(out_path, 'wb').close()
+                if out_format == 'bam':
+                    misc.write_bam_header(out_path)
+                else:
+                    open(out_path, 'wb').close()
 
         reader = threading.Thread(target=produce, daemon=True)
         writer = threading.Thread(target=consume_writes, daemon=True)
@@ -394,7 +416,7 @@ class FileTrimmer(object):
         self._tick('write_wait', t)
         if errors:
             raise errors[0]
-        if _bgzf_mode(self, out_format):
+        if _finish_mode(self, out_format):
             for path in [out_path] + [p for p, _ in bins.values()]:
                 if os.path.isfile(path):
                     misc.bgzf_finish(path)
@@ -419,7 +441,7 @@ class FileTrimmer(object):
             emitted = misc.write_reads(b, path, out_format, st, et, None, self.min_split, self.discard_middle,
                                        untrimmed=self.untrimmed, select=mask, append=not fresh, cut_arrays=(co, cu),
                                        gzip_device=getattr(self, 'gzip_device', None),
-                                         bgzf=_bgzf_mode(self, out_format))
+                                       bgzf=_bgzf_mode(self, out_format), **_bam_kw(self, out_format, b))
             if emitted == 0:
                 if fresh and os.path.exists(path):
                     os.remove(path)             # the reference never opens an empty bin

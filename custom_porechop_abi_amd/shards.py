@@ -404,6 +404,8 @@ def trim_file_sharded(in_path, out_path, out_format='fastq', scoring_scheme_vals
     from . import misc
     if bgzf:
         raise ValueError('BGZF output is not available for sharded runs: use pipeline.FileTrimmer(bgzf=True)')
+    if out_format == 'bam':
+        raise ValueError('BAM output is not available for sharded runs: use pipeline.FileTrimmer.trim_file')
     if os.path.isfile(in_path) and misc.is_bam(in_path):
         raise ValueError('BAM input is not available for sharded runs: use pipeline.FileTrimmer.trim_file')
     dist = _dist()

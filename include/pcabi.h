@@ -693,7 +693,9 @@ int pcabi_reads_write_dev(const pcabi_reads *b, const char *path, int append, in
                           const int64_t *cuts, int min_split_read_size, int discard_middle,
                           int untrimmed, const uint8_t *select, int gzip_device);
 /* Seconds the calling thread's last pcabi_reads_write / _dev call spent laying out the records (plain
- * files and gz = 2), compressing on the device (gz = 2) and writing the file (tools/gz_timing.py). */
+ * files and gz = 2), compressing on the device (gz = 2) and writing the file (tools/gz_timing.py); after
+ * pcabi_reads_write_bam: the part table, side blob and plan (and the host pack when device < 0), the
+ * device call or zlib, and writing the file (tools/bam_write_timing.py). */
 void pcabi_reads_write_last_times(double *layout, double *compress, double *write);
 
 /* ---- gzip on the device (csrc/pcabi_deflate.hip) ----------------------------------------
@@ -745,12 +747,18 @@ void pcabi_gzip_last_times(double *copy_in, double *wait, double *copy_out);
  *   pcabi_bgzf_bound : capacity that always suffices (n_blocks = 0: fixed blocks).
  *   pcabi_bgzf_host  : as pcabi_gzip_host; eof != 0 appends the standard 28-byte end-of-file member
  *       (1f8b08040000000000ff0600424302001b0003000000000000000000). No bytes give no member.
+ *   pcabi_bgzf_dev   : as pcabi_gzip_dev (device pointers, asynchronous, no host synchronisation):
+ *       in[0, n) in members of block_len (1..65280) bytes, the last one shorter; scratch of
+ *       pcabi_bgzf_scratch_bytes(n, block_len). No marker. The BAM writer's encoder entry.
  *   pcabi_bgzf_write_eof : appends that marker to a file.
  *   pcabi_reads_write_dev(..., gz = 3, ...) is the record writer in this mode (blocks planned with cap
  *       65280); it never writes the marker, so appended batches stay one contiguous chain. */
 int64_t pcabi_bgzf_bound(int64_t n, int64_t n_blocks, int eof);
 int64_t pcabi_bgzf_host(int device, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks, int eof,
                         uint8_t *out, int64_t cap);
+int64_t pcabi_bgzf_scratch_bytes(int64_t n, int64_t block_len);
+int pcabi_bgzf_dev(void *stream, const uint8_t *in, int64_t n, int64_t block_len, uint8_t *out, int64_t cap,
+                   int64_t *out_len, void *scratch, int64_t scratch_len);
 int pcabi_bgzf_write_eof(const char *path);
 
 /* ---- gunzip on the device (csrc/pcabi_inflate.hip) --------------------------------------
@@ -808,7 +816,7 @@ void pcabi_gunzip_last_times(double *copy_in, double *wait, double *copy_out);
  * first four decoded bytes are "BAM\1". Batches are PCABI_FASTQ batches: name = read name, sequence
  * letters over "=ACMGRSVTWYHKDBN", qualities q + 33 ('+' for every base when they are absent), rna 0,
  * empty spacer; secondary (0x100) and supplementary (0x800) records are skipped, reverse-strand
- * records (0x10) are reverse-complemented, tags are dropped. pcabi_fastx_open_dev unpacks the
+ * records (0x10) are reverse-complemented, tags are dropped unless pcabi_fastx_keep_aux asks for them. pcabi_fastx_open_dev unpacks the
  * records on the device next to the inflated bytes. pcabi_fastx_remaining returns -1;
  * pcabi_fastx_set_range, pcabi_fastx_record_start and pcabi_fastx_next_text refuse a BAM reader
  * (PCABI_E_ARG). An invalid record, a truncated record chain, a member that does not inflate or
@@ -855,6 +863,84 @@ int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi
                           uint8_t *seq, int64_t seq_cap, uint8_t *qual, int64_t qual_cap, uint8_t *codes,
                           int64_t codes_cap, int64_t tail_off);
 void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
+
+/* ---- unaligned BAM output (csrc/pcabi_bam.h, csrc/pcabi_bam.hip, csrc/pcabi_io.cpp) ----------
+ * The inverse of the unpack: parts of a batch (whole reads, trimmed reads, split pieces) laid out as
+ * a chain of unmapped BAM records. One pcabi_bam_part per output record; a record is
+ *   block_size | refID -1 | pos -1 | l_read_name = name_len + 1 | mapq 0 | bin 4680 | n_cigar_op 0 |
+ *   flag 4 | l_seq | next_refID -1 | next_pos -1 | tlen 0 | name NUL | seq u8[(l_seq + 1) / 2] |
+ *   qual u8[l_seq] | aux
+ * of 36 + name_len + 1 + (l_seq + 1) / 2 + l_seq + aux_len bytes. Letters become codes over
+ * "=ACMGRSVTWYHKDBN" (U -> T, any other byte -> N), the earlier base in the high nibble, the low
+ * nibble of an odd last byte 0; qualities are the character - 33 clamped to 0..93, or 0xFF for every
+ * base when qual_src < 0. The name and the aux bytes of a part lie back to back in a side blob.
+ *   pcabi_bam_pack_plan : (host) fills out / tile0 of parts[0, n_parts) for a chain that starts at
+ *       out0 and returns the chain's end; tiles[0] (may be NULL) = the tile count. Every part owns
+ *       max(1, ceil(l_seq / 16384)) tiles. PCABI_E_ARG for a negative length or a name over 254 bytes.
+ *   pcabi_bam_pack_dev  : device pointers on the current device, asynchronous on `stream`: the parts
+ *       (a planned table, tile0 ascending) from seq[0, seq_n) / qual[0, qual_n) / side[0, side_n)
+ *       into out[0, out_cap). A part writes its own record's bytes only; a part that does not lie
+ *       inside the buffers writes nothing. Returns 0 or PCABI_E_ARG.
+ *   pcabi_bam_pack_host : the same with host buffers, staged through the device; device < 0 runs the
+ *       host build of the same code (no GPU needed). Table entries outside the buffers, or not
+ *       planned, are refused (PCABI_E_ARG). On the device the output starts as far off a 16-byte
+ *       boundary as the caller's pointer and lies between 64 guard bytes, which are checked after the
+ *       kernel (PCABI_E_DEVICE if it wrote outside). Bytes no part owns keep their values.
+ *   pcabi_bam_pack_last_times : milliseconds k_bam_pack took (device events) and the bytes it read
+ *       and wrote since the last call with reset != 0, counted while pcabi_bam_last_times' profiling
+ *       is on.
+ *   pcabi_reads_write_bam : pcabi_reads_write_dev's arguments (without gz and fasta) for a BAM file.
+ *       The same parts as the text writers': trims, split parts, "_k" names, min_split_read_size,
+ *       discard_middle, untrimmed, select, and the same return value. A record's name is the header
+ *       up to its first space or tab (the rest of the header is dropped), cut to 254 bytes, "*" when
+ *       empty; an RNA read's bases are written as T; a FASTA batch writes absent qualities (0xFF); a
+ *       quality-less FASTQ record's '+' padding is written as Phred 10. append == 0 first writes the
+ *       BAM header: "BAM\1", header_text[0, header_len) ("@HD\tVN:1.6\tSO:unknown\n" when NULL),
+ *       n_ref = 0. The header and the record chain are one byte stream, cut into BGZF members of
+ *       65280 bytes (the last one shorter; records may span members). No end-of-file marker is
+ *       written: pcabi_bgzf_write_eof finishes the file, so batches can be appended. device >= 0:
+ *       the text, the part table and the side blob go up, k_bam_pack writes the stream into device
+ *       memory, the BGZF encoder reads it there and only compressed bytes come back; device < 0: the
+ *       host build of the pack and zlib raw deflate per member on the io threads. Both inflate to the
+ *       same bytes. keep_aux != 0 writes the aux tags a BAM reader kept (pcabi_fastx_keep_aux): a
+ *       part that is its whole read, with the read's bases as stored, gets them verbatim; any other
+ *       part gets them without the position-dependent tags MM ML MN Mm Ml mv, which are dropped and
+ *       not recomputed.
+ *   pcabi_fastx_keep_aux : before the first pcabi_fastx_next, on = 1 makes a BAM reader keep every
+ *       kept record's aux bytes and whether its bases are stored as written (not reverse-strand); any
+ *       other input: no effect. A record whose aux chain does not walk (types A c C s S i I f Z H B)
+ *       is then PCABI_E_PARSE, raised after the records before it.
+ *   pcabi_reads_aux : a batch's aux bytes: read i's are aux[aux_off[i], aux_off[i + 1]); as_stored[i].
+ *       All three NULL when the batch holds none.
+ *   pcabi_fastx_bam_header : a BAM reader's header text (valid until close) once a batch was read;
+ *       *len = 0 for any other input.
+ */
+typedef struct pcabi_bam_part {
+    int64_t seq_src;    /* base 0 in the sequence buffer (one letter per byte)                   */
+    int64_t qual_src;   /* base 0 in the quality buffer (character = q + 33); < 0: absent, 0xFF  */
+    int64_t side_off;   /* the name (name_len bytes), then the aux bytes (aux_len), in the blob  */
+    int64_t out;        /* the record's start (its block_size field) in the output stream        */
+    int64_t tile0;      /* tiles of the parts before this one (16384 bases; at least one a part) */
+    int32_t l_seq;
+    int32_t name_len;
+    int32_t aux_len;
+    int32_t reserved;
+} pcabi_bam_part;
+int64_t pcabi_bam_pack_plan(pcabi_bam_part *parts, int64_t n_parts, int64_t out0, int64_t *tiles);
+int pcabi_bam_pack_dev(void *stream, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                       const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                       int64_t n_tiles, uint8_t *out, int64_t out_cap);
+int pcabi_bam_pack_host(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                        const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                        uint8_t *out, int64_t out_cap);
+void pcabi_bam_pack_last_times(int reset, double *ms, int64_t *bytes);
+int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
+                          const int32_t *end_trim, const int64_t *cut_off, const int64_t *cuts,
+                          int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
+                          const char *header_text, int64_t header_len, int keep_aux, int device);
+int pcabi_fastx_keep_aux(pcabi_fastx *r, int on);
+int pcabi_reads_aux(const pcabi_reads *b, const uint8_t **aux, const int64_t **aux_off, const uint8_t **as_stored);
+int pcabi_fastx_bam_header(const pcabi_fastx *r, const char **text, int64_t *len);
 
 #ifdef __cplusplus
 }
