@@ -24,18 +24,10 @@
 
 #include "../../include/pcabi.h"
 #include "pcabi_bam.h"
+#include "pcabi_hostdev.h"
 
-namespace pcabi_internal {
-int fail(int code, const std::string &msg);
-}
-using pcabi_internal::fail;
+using namespace pcabi_internal;
 using namespace pcabi_bam;
-
-#define BAM_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return fail(PCABI_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -87,7 +79,7 @@ int launch(hipStream_t st, const uint8_t *bam, int64_t n, const pcabi_bam_rec *r
     const int64_t tiles = n_recs > 0 ? n_tiles : 0;
     hipLaunchKernelGGL(k_bam_unpack, dim3((unsigned)(tiles + 1)), dim3(kLanes), 0, st, bam, n, recs, n_recs, tiles, seq,
                        seq_cap, qual, qual_cap, codes, codes_cap, tail_off);
-    BAM_TRY(hipGetLastError());
+    PCABI_TRY(hipGetLastError());
     return 0;
 }
 
@@ -147,7 +139,7 @@ int launch_pack(hipStream_t st, const uint8_t *seq, int64_t seq_n, const uint8_t
     if (n_parts <= 0 || n_tiles == 0) return 0;
     hipLaunchKernelGGL(k_bam_pack, dim3((unsigned)n_tiles), dim3(kLanes), 0, st, seq, seq_n, qual, qual_n, side, side_n, parts,
                        n_parts, n_tiles, out, out_cap);
-    BAM_TRY(hipGetLastError());
+    PCABI_TRY(hipGetLastError());
     return 0;
 }
 
@@ -210,17 +202,16 @@ void prof_end(void *stream, void *span) {
 // the newest group), the record table and the three outputs, which come back through pinned memory.
 struct BamDev {
     int device = 0;
-    uint8_t *win[2] = {nullptr, nullptr};   // the window, ping-pong: the carry moves between them
-    int64_t cap[2] = {0, 0};
+    DevBuf<> win[2];                        // the window, ping-pong: the carry moves between them
     int cur = 0;
     int64_t len = 0;
-    hipStream_t st = nullptr;               // the stream of the newest group
+    hipStream_t st = nullptr;               // the stream of the newest group (the GunzipReader's)
     hipEvent_t moved = nullptr;             // recorded on st behind the window's copies
     bool moved_set = false;
-    pcabi_bam_rec *d_recs = nullptr, *p_recs = nullptr;
-    int64_t recs_cap = 0;
-    uint8_t *d_out = nullptr, *p_out = nullptr;
-    int64_t out_cap = 0;
+    DevBuf<pcabi_bam_rec> d_recs;
+    PinBuf<pcabi_bam_rec> p_recs;
+    DevBuf<> d_out;
+    PinBuf<> p_out;
 };
 
 int bam_dev_open(int device, BamDev **out) {
@@ -236,12 +227,6 @@ void bam_dev_close(BamDev *b) {
     if (b->moved_set) (void)hipEventSynchronize(b->moved);
     if (b->st) (void)hipStreamSynchronize(b->st);
     if (b->moved) (void)hipEventDestroy(b->moved);
-    for (int k = 0; k < 2; ++k)
-        if (b->win[k]) (void)hipFree(b->win[k]);
-    if (b->d_recs) (void)hipFree(b->d_recs);
-    if (b->p_recs) (void)hipHostFree(b->p_recs);
-    if (b->d_out) (void)hipFree(b->d_out);
-    if (b->p_out) (void)hipHostFree(b->p_out);
     delete b;
 }
 
@@ -250,29 +235,22 @@ void bam_dev_close(BamDev *b) {
 // copies wait for the event behind the last window copies alone, never for that stream, so the inflate
 // runs on beside them and beside the unpack.
 int bam_dev_append(BamDev *b, int64_t keep_from, const uint8_t *src, int64_t n, void *stream) {
-    BAM_TRY(hipSetDevice(b->device));
+    PCABI_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)stream;
-    if (!b->moved) BAM_TRY(hipEventCreateWithFlags(&b->moved, hipEventDisableTiming));
-    if (b->moved_set && b->st != st) BAM_TRY(hipStreamWaitEvent(st, b->moved, 0));
+    if (!b->moved) PCABI_TRY(hipEventCreateWithFlags(&b->moved, hipEventDisableTiming));
+    if (b->moved_set && b->st != st) PCABI_TRY(hipStreamWaitEvent(st, b->moved, 0));
     b->st = st;
     if (keep_from < 0 || keep_from > b->len || n < 0) return fail(PCABI_E_ARG, "bad window");
     const int64_t carry = b->len - keep_from, need = carry + n + 64;
     const int nxt = b->cur ^ 1;
-    if (b->cap[nxt] < need) {
-        if (b->win[nxt]) BAM_TRY(hipFree(b->win[nxt]));
-        b->win[nxt] = nullptr;
-        b->cap[nxt] = 0;
-        const int64_t want = std::max<int64_t>(need + need / 2, 1 << 20);
-        BAM_TRY(hipMalloc((void **)&b->win[nxt], (size_t)want));
-        b->cap[nxt] = want;
-    }
+    if (int rc = b->win[nxt].reserve(need, std::max<int64_t>(need + need / 2, 1 << 20))) return rc;
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 2) : nullptr;
     if (carry > 0)
-        BAM_TRY(hipMemcpyAsync(b->win[nxt], b->win[b->cur] + keep_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
-    if (n > 0) BAM_TRY(hipMemcpyAsync(b->win[nxt] + carry, src, (size_t)n, hipMemcpyDeviceToDevice, st));
+        PCABI_TRY(hipMemcpyAsync(b->win[nxt], b->win[b->cur] + keep_from, (size_t)carry, hipMemcpyDeviceToDevice, st));
+    if (n > 0) PCABI_TRY(hipMemcpyAsync(b->win[nxt] + carry, src, (size_t)n, hipMemcpyDeviceToDevice, st));
     if (prof) prof_end(st, sp);
-    BAM_TRY(hipEventRecord(b->moved, st));
+    PCABI_TRY(hipEventRecord(b->moved, st));
     b->moved_set = true;
     b->cur = nxt;
     b->len = carry + n;
@@ -284,35 +262,20 @@ int bam_dev_append(BamDev *b, int64_t keep_from, const uint8_t *src, int64_t n, 
 // Synchronises.
 int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const Layout &lay, const uint8_t **seq,
                    const uint8_t **qual, const uint8_t **codes) {
-    BAM_TRY(hipSetDevice(b->device));
+    PCABI_TRY(hipSetDevice(b->device));
     hipStream_t st = b->st;
-    if (n_recs > b->recs_cap) {
-        if (b->d_recs) BAM_TRY(hipFree(b->d_recs));
-        if (b->p_recs) BAM_TRY(hipHostFree(b->p_recs));
-        b->d_recs = b->p_recs = nullptr;
-        b->recs_cap = 0;
-        const int64_t want = std::max<int64_t>(n_recs + n_recs / 2, 1024);
-        BAM_TRY(hipMalloc((void **)&b->d_recs, (size_t)want * sizeof(pcabi_bam_rec)));
-        BAM_TRY(hipHostMalloc((void **)&b->p_recs, (size_t)want * sizeof(pcabi_bam_rec), hipHostMallocDefault));
-        b->recs_cap = want;
-    }
+    const int64_t recs_want = std::max<int64_t>(n_recs + n_recs / 2, 1024);
+    if (int rc = b->d_recs.reserve(n_recs, recs_want)) return rc;
+    if (int rc = b->p_recs.reserve(n_recs, recs_want)) return rc;
     // seq | qual | codes, each region's start 256-aligned
     const int64_t seq_sz = (lay.seq + 255) & ~(int64_t)255, code_sz = (lay.code + 255) & ~(int64_t)255;
-    const int64_t total = 2 * seq_sz + code_sz + 256;
-    if (total > b->out_cap) {
-        if (b->d_out) BAM_TRY(hipFree(b->d_out));
-        if (b->p_out) BAM_TRY(hipHostFree(b->p_out));
-        b->d_out = b->p_out = nullptr;
-        b->out_cap = 0;
-        const int64_t want = std::max<int64_t>(total + total / 4, 1 << 20);
-        BAM_TRY(hipMalloc((void **)&b->d_out, (size_t)want));
-        BAM_TRY(hipHostMalloc((void **)&b->p_out, (size_t)want, hipHostMallocDefault));
-        b->out_cap = want;
-    }
+    const int64_t total = 2 * seq_sz + code_sz + 256, out_want = std::max<int64_t>(total + total / 4, 1 << 20);
+    if (int rc = b->d_out.reserve(total, out_want)) return rc;
+    if (int rc = b->p_out.reserve(total, out_want)) return rc;
     std::memcpy(b->p_recs, recs, (size_t)n_recs * sizeof(pcabi_bam_rec));
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 2) : nullptr;
-    BAM_TRY(hipMemcpyAsync(b->d_recs, b->p_recs, (size_t)n_recs * sizeof(pcabi_bam_rec), hipMemcpyHostToDevice, st));
+    PCABI_TRY(hipMemcpyAsync(b->d_recs, b->p_recs, (size_t)n_recs * sizeof(pcabi_bam_rec), hipMemcpyHostToDevice, st));
     if (prof) prof_end(st, sp), sp = prof_begin(st, 1);
     if (int rc = launch(st, b->win[b->cur], b->len, b->d_recs, n_recs, lay.tiles, b->d_out, lay.seq, b->d_out + seq_sz,
                         lay.seq, b->d_out + 2 * seq_sz, lay.code, -1))
@@ -320,16 +283,16 @@ int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const L
     if (prof) prof_end(st, sp), sp = prof_begin(st, 3);
     // the three regions' used bytes come back in one copy when they are small, else one each
     if (lay.seq > 0) {
-        BAM_TRY(hipMemcpyAsync(b->p_out, b->d_out, (size_t)lay.seq, hipMemcpyDeviceToHost, st));
-        BAM_TRY(hipMemcpyAsync(b->p_out + seq_sz, b->d_out + seq_sz, (size_t)lay.seq, hipMemcpyDeviceToHost, st));
-        BAM_TRY(hipMemcpyAsync(b->p_out + 2 * seq_sz, b->d_out + 2 * seq_sz, (size_t)lay.code, hipMemcpyDeviceToHost, st));
+        PCABI_TRY(hipMemcpyAsync(b->p_out, b->d_out, (size_t)lay.seq, hipMemcpyDeviceToHost, st));
+        PCABI_TRY(hipMemcpyAsync(b->p_out + seq_sz, b->d_out + seq_sz, (size_t)lay.seq, hipMemcpyDeviceToHost, st));
+        PCABI_TRY(hipMemcpyAsync(b->p_out + 2 * seq_sz, b->d_out + 2 * seq_sz, (size_t)lay.code, hipMemcpyDeviceToHost, st));
     }
     if (prof) {
         prof_end(st, sp);
         std::lock_guard<std::mutex> lk(g_prof_mu);
         g_unpack_bytes += (lay.seq + 1) / 2 + lay.seq + 2 * lay.seq + lay.code + n_recs * (int64_t)sizeof(pcabi_bam_rec);
     }
-    BAM_TRY(hipStreamSynchronize(st));
+    PCABI_TRY(hipStreamSynchronize(st));
     *seq = b->p_out;
     *qual = b->p_out + seq_sz;
     *codes = b->p_out + 2 * seq_sz;
@@ -346,61 +309,33 @@ int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const L
 namespace {
 struct PackDev {
     int device = -1;
-    uint8_t *buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // seq, qual, side, parts, stream, z
-    int64_t cap[6] = {0, 0, 0, 0, 0, 0};
-    void *scratch = nullptr;
-    int64_t scratch_cap = 0;
-    int64_t *d_len = nullptr;
-    uint8_t *p_z = nullptr;   // the compressed bytes, pinned
-    int64_t p_z_cap = 0;
-    hipStream_t st = nullptr;
-} g_pack;
+    DevBuf<> buf[6];   // seq, qual, side, parts, stream, z
+    DevBuf<> scratch;
+    DevBuf<int64_t> d_len;
+    PinBuf<> p_z;      // the compressed bytes, pinned
+    Stream st;
+};
+// kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
+// HIP runtime that may already have shut down
+PackDev &g_pack = *new PackDev;
 std::mutex g_pack_mu;
-
-void pack_dev_free() {
-    for (int k = 0; k < 6; ++k) {
-        if (g_pack.buf[k]) (void)hipFree(g_pack.buf[k]);
-        g_pack.buf[k] = nullptr;
-        g_pack.cap[k] = 0;
-    }
-    if (g_pack.scratch) (void)hipFree(g_pack.scratch);
-    if (g_pack.d_len) (void)hipFree(g_pack.d_len);
-    if (g_pack.p_z) (void)hipHostFree(g_pack.p_z);
-    g_pack.p_z = nullptr;
-    g_pack.p_z_cap = 0;
-    if (g_pack.st) (void)hipStreamDestroy(g_pack.st);
-    g_pack.scratch = nullptr;
-    g_pack.d_len = nullptr;
-    g_pack.st = nullptr;
-    g_pack.scratch_cap = 0;
-    g_pack.device = -1;
-}
-
-int pack_dev_room(uint8_t **p, int64_t *cap, int64_t need) {
-    if (*cap >= need) return 0;
-    if (*p) BAM_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const int64_t want = std::max<int64_t>(need + need / 4, 1 << 20);
-    BAM_TRY(hipMalloc((void **)p, (size_t)want));
-    *cap = want;
-    return 0;
-}
 }  // namespace
 
 int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
                       int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
                       int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink) {
     std::lock_guard<std::mutex> lk(g_pack_mu);
-    if (device < 0) BAM_TRY(hipGetDevice(&device));
+    if (device < 0) PCABI_TRY(hipGetDevice(&device));
     if (g_pack.device >= 0 && g_pack.device != device) {
         (void)hipSetDevice(g_pack.device);
-        pack_dev_free();
+        g_pack.st.release();
+        g_pack = PackDev();
     }
-    BAM_TRY(hipSetDevice(device));
+    PCABI_TRY(hipSetDevice(device));
     g_pack.device = device;
-    if (!g_pack.st) BAM_TRY(hipStreamCreateWithFlags(&g_pack.st, hipStreamNonBlocking));
-    if (!g_pack.d_len) BAM_TRY(hipMalloc((void **)&g_pack.d_len, 64));
+    if (!g_pack.st)
+        if (int rc = g_pack.st.create()) return rc;
+    if (int rc = g_pack.d_len.reserve(8, 8)) return rc;
     hipStream_t st = g_pack.st;
     const int64_t block = PCABI_BGZF_BLOCK_CAP;
     const int64_t z_cap = pcabi_bgzf_bound(stream_n, std::max<int64_t>((stream_n + block - 1) / block, 1), 0);
@@ -409,23 +344,17 @@ int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uin
     const int64_t need[6] = {seq_n + 64, qual_n + 64, side_n + 64, n_parts * (int64_t)sizeof(pcabi_bam_part) + 64,
                              stream_n + 64, z_cap + 64};
     for (int k = 0; k < 6; ++k)
-        if (int rc = pack_dev_room(&g_pack.buf[k], &g_pack.cap[k], need[k])) return rc;
-    if (g_pack.scratch_cap < sc) {
-        if (g_pack.scratch) BAM_TRY(hipFree(g_pack.scratch));
-        g_pack.scratch = nullptr;
-        g_pack.scratch_cap = 0;
-        BAM_TRY(hipMalloc(&g_pack.scratch, (size_t)sc + sc / 4));
-        g_pack.scratch_cap = sc + sc / 4;
-    }
+        if (int rc = g_pack.buf[k].reserve(need[k], std::max<int64_t>(need[k] + need[k] / 4, 1 << 20))) return rc;
+    if (int rc = g_pack.scratch.reserve(sc, sc + sc / 4)) return rc;
     uint8_t *d_seq = g_pack.buf[0], *d_qual = g_pack.buf[1], *d_side = g_pack.buf[2], *d_stream = g_pack.buf[4],
             *d_z = g_pack.buf[5];
-    pcabi_bam_part *d_parts = (pcabi_bam_part *)g_pack.buf[3];
-    if (seq_n > 0) BAM_TRY(hipMemcpyAsync(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
-    if (qual_n > 0) BAM_TRY(hipMemcpyAsync(d_qual, qual, (size_t)qual_n, hipMemcpyHostToDevice, st));
-    if (side_n > 0) BAM_TRY(hipMemcpyAsync(d_side, side, (size_t)side_n, hipMemcpyHostToDevice, st));
+    pcabi_bam_part *d_parts = (pcabi_bam_part *)g_pack.buf[3].p;
+    if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
+    if (qual_n > 0) PCABI_TRY(hipMemcpyAsync(d_qual, qual, (size_t)qual_n, hipMemcpyHostToDevice, st));
+    if (side_n > 0) PCABI_TRY(hipMemcpyAsync(d_side, side, (size_t)side_n, hipMemcpyHostToDevice, st));
     if (n_parts > 0)
-        BAM_TRY(hipMemcpyAsync(d_parts, parts, (size_t)n_parts * sizeof(pcabi_bam_part), hipMemcpyHostToDevice, st));
-    if (head_n > 0) BAM_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
+        PCABI_TRY(hipMemcpyAsync(d_parts, parts, (size_t)n_parts * sizeof(pcabi_bam_part), hipMemcpyHostToDevice, st));
+    if (head_n > 0) PCABI_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 4) : nullptr;
     if (int rc = launch_pack(st, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, n_tiles, d_stream, stream_n))
@@ -436,22 +365,15 @@ int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uin
         for (int64_t i = 0; i < n_parts; ++i) g_pack_bytes += 2 * (int64_t)parts[i].l_seq + part_size(parts[i]);
         g_pack_bytes += n_parts * (int64_t)sizeof(pcabi_bam_part);
     }
-    if (int rc = pcabi_bgzf_dev(st, d_stream, stream_n, block, d_z, z_cap, g_pack.d_len, g_pack.scratch, g_pack.scratch_cap))
+    if (int rc = pcabi_bgzf_dev(st, d_stream, stream_n, block, d_z, z_cap, g_pack.d_len, g_pack.scratch, g_pack.scratch.cap))
         return rc;
     int64_t zn = 0;
-    BAM_TRY(hipMemcpyAsync(&zn, g_pack.d_len, 8, hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipStreamSynchronize(st));
+    PCABI_TRY(hipMemcpyAsync(&zn, g_pack.d_len, 8, hipMemcpyDeviceToHost, st));
+    PCABI_TRY(hipStreamSynchronize(st));
     if (zn < 0 || zn > z_cap) return fail(PCABI_E_DEVICE, "the BGZF encoder refused the stream");
-    if (g_pack.p_z_cap < zn) {
-        if (g_pack.p_z) BAM_TRY(hipHostFree(g_pack.p_z));
-        g_pack.p_z = nullptr;
-        g_pack.p_z_cap = 0;
-        const int64_t want = std::max<int64_t>(zn + zn / 4, 1 << 20);
-        BAM_TRY(hipHostMalloc((void **)&g_pack.p_z, (size_t)want, hipHostMallocDefault));
-        g_pack.p_z_cap = want;
-    }
-    if (zn > 0) BAM_TRY(hipMemcpyAsync(g_pack.p_z, d_z, (size_t)zn, hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipStreamSynchronize(st));
+    if (int rc = g_pack.p_z.reserve(zn, std::max<int64_t>(zn + zn / 4, 1 << 20))) return rc;
+    if (zn > 0) PCABI_TRY(hipMemcpyAsync(g_pack.p_z, d_z, (size_t)zn, hipMemcpyDeviceToHost, st));
+    PCABI_TRY(hipStreamSynchronize(st));
     sink(g_pack.p_z, zn);
     return zn;
 }
@@ -512,21 +434,20 @@ int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi
         if (tail_off >= 0) std::memset(codes + tail_off, 4, 16);
         return 0;
     }
-    BAM_TRY(hipSetDevice(device));
+    PCABI_TRY(hipSetDevice(device));
     // every output sits between 64 guard bytes on the device, checked after the kernel; bytes no record
     // owns go up and come back as they were
     constexpr int64_t kGuard = 64;
     uint8_t *host_out[3] = {seq, qual, codes};
     const int64_t caps[3] = {seq_cap, qual_cap, codes_cap};
     std::vector<uint8_t> stage[3];
-    uint8_t *d_bam = nullptr, *d_out[3] = {nullptr, nullptr, nullptr};
-    pcabi_bam_rec *d_recs = nullptr;
-    int rc = 0;
+    DevBuf<> d_bam, d_out[3];
+    DevBuf<pcabi_bam_rec> d_recs;
+    int rc = d_bam.reserve(n + 64, n + 64);
+    if (!rc) rc = d_recs.reserve(n_recs + 1, n_recs + 1);
     auto step = [&](hipError_t e, const char *what) {
         if (!rc && e != hipSuccess) rc = fail(PCABI_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     };
-    step(hipMalloc((void **)&d_bam, (size_t)n + 64), "hipMalloc");
-    step(hipMalloc((void **)&d_recs, (size_t)(n_recs + 1) * sizeof(pcabi_bam_rec)), "hipMalloc");
     if (!rc && n > 0) step(hipMemcpy(d_bam, bam, (size_t)n, hipMemcpyHostToDevice), "hipMemcpy");
     if (!rc && n_recs > 0)
         step(hipMemcpy(d_recs, recs, (size_t)n_recs * sizeof(pcabi_bam_rec), hipMemcpyHostToDevice), "hipMemcpy");
@@ -535,7 +456,7 @@ int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi
         base[o] = kGuard + (int64_t)((uintptr_t)host_out[o] & 15u);
         stage[o].assign((size_t)(base[o] + caps[o] + kGuard), 0xA5);
         if (caps[o] > 0) std::memcpy(stage[o].data() + base[o], host_out[o], (size_t)caps[o]);
-        step(hipMalloc((void **)&d_out[o], stage[o].size()), "hipMalloc");
+        if (!rc) rc = d_out[o].reserve((int64_t)stage[o].size(), (int64_t)stage[o].size());
         if (!rc) step(hipMemcpy(d_out[o], stage[o].data(), stage[o].size(), hipMemcpyHostToDevice), "hipMemcpy");
     }
     if (!rc)
@@ -554,9 +475,6 @@ int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi
     if (!rc)
         for (int o = 0; o < 3; ++o)
             if (caps[o] > 0) std::memcpy(host_out[o], stage[o].data() + base[o], (size_t)caps[o]);
-    (void)hipFree(d_bam);
-    (void)hipFree(d_recs);
-    for (int o = 0; o < 3; ++o) (void)hipFree(d_out[o]);
     return rc;
 }
 
@@ -613,40 +531,36 @@ int pcabi_bam_pack_host(int device, const uint8_t *seq, int64_t seq_n, const uin
         for (int64_t i = 0; i < n_parts; ++i) pack_part(parts[i], seq, qual, side, out);
         return 0;
     }
-    BAM_TRY(hipSetDevice(device));
+    PCABI_TRY(hipSetDevice(device));
     // the output sits between 64 guard bytes on the device, checked after the kernel; bytes no part
     // owns go up and come back as they were
     constexpr int64_t kGuard = 64;
     const int64_t base = kGuard + (int64_t)((uintptr_t)out & 15u);   // as far off a 16-byte boundary as the caller's pointer
     std::vector<uint8_t> stage((size_t)(base + out_cap + kGuard), 0xA5);
     if (out_cap > 0) std::memcpy(stage.data() + base, out, (size_t)out_cap);
-    uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_side = nullptr, *d_out = nullptr;
-    pcabi_bam_part *d_parts = nullptr;
+    DevBuf<> d_seq, d_qual, d_side, d_parts, d_out;
     int rc = 0;
     auto step = [&](hipError_t e, const char *what) {
         if (!rc && e != hipSuccess) rc = fail(PCABI_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
     };
-    auto up = [&](uint8_t **d, const void *h, int64_t n) {
-        step(hipMalloc((void **)d, (size_t)n + 64), "hipMalloc");
-        if (!rc && n > 0) step(hipMemcpy(*d, h, (size_t)n, hipMemcpyHostToDevice), "hipMemcpy");
+    auto up = [&](DevBuf<> &d, const void *h, int64_t n) {
+        if (!rc) rc = d.reserve(n + 64, n + 64);
+        if (!rc && n > 0) step(hipMemcpy(d, h, (size_t)n, hipMemcpyHostToDevice), "hipMemcpy");
     };
-    up(&d_seq, seq, seq_n);
-    up(&d_qual, qual, qual_n);
-    up(&d_side, side, side_n);
-    up((uint8_t **)&d_parts, parts, n_parts * (int64_t)sizeof(pcabi_bam_part));
-    up(&d_out, stage.data(), (int64_t)stage.size());
-    if (!rc) rc = launch_pack(nullptr, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, tiles, d_out + base, out_cap);
+    up(d_seq, seq, seq_n);
+    up(d_qual, qual, qual_n);
+    up(d_side, side, side_n);
+    up(d_parts, parts, n_parts * (int64_t)sizeof(pcabi_bam_part));
+    up(d_out, stage.data(), (int64_t)stage.size());
+    if (!rc)
+        rc = launch_pack(nullptr, d_seq, seq_n, d_qual, qual_n, d_side, side_n, (const pcabi_bam_part *)d_parts.p, n_parts, tiles,
+                         d_out + base, out_cap);
     if (!rc) step(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
     if (!rc) step(hipMemcpy(stage.data(), d_out, stage.size(), hipMemcpyDeviceToHost), "hipMemcpy");
     for (int64_t g = 0; g < kGuard && !rc; ++g)
         if (stage[(size_t)(base - 1 - g)] != 0xA5 || stage[(size_t)(base + out_cap + g)] != 0xA5)
             rc = fail(PCABI_E_DEVICE, "k_bam_pack wrote outside its output");
     if (!rc && out_cap > 0) std::memcpy(out, stage.data() + base, (size_t)out_cap);
-    (void)hipFree(d_seq);
-    (void)hipFree(d_qual);
-    (void)hipFree(d_side);
-    (void)hipFree(d_parts);
-    (void)hipFree(d_out);
     return rc;
 }
 

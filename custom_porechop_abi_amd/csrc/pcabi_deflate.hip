@@ -28,25 +28,16 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/pcabi.h"
 #include "pcabi_crc.h"
 #include "pcabi_deflate.h"
+#include "pcabi_hostdev.h"
 
-namespace pcabi_internal {
-int fail(int code, const std::string &msg);
-}
-using pcabi_internal::fail;
+using namespace pcabi_internal;
 using namespace pcabi_deflate;
 using namespace pcabi_crc;
-
-#define GZ_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return fail(PCABI_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -481,7 +472,7 @@ int launch(hipStream_t st, const uint8_t *in, int64_t n, const int64_t *block_of
     uint32_t *hdr = (uint32_t *)p;
     p += 4ll * kHdrWords * nb;
     uint32_t *tbl = (uint32_t *)p;
-    GZ_TRY(hipMemsetAsync(ctl, 0, 64, st));
+    PCABI_TRY(hipMemsetAsync(ctl, 0, 64, st));
     if (nb > 0) hipLaunchKernelGGL(k_plan, dim3((unsigned)nb), dim3(kThreads), 0, st, in, n, block_off, nb, fixed, tbl, hdr, info, ctl);
     hipLaunchKernelGGL(k_offsets, dim3(1), dim3(1024), 0, st, info, nb, member_blocks, mhdr, cap, out_off, ctl, out_len_dev);
     const int64_t nm = std::max<int64_t>(1, (nb + member_blocks - 1) / member_blocks);
@@ -491,92 +482,58 @@ int launch(hipStream_t st, const uint8_t *in, int64_t n, const int64_t *block_of
     if (nb > 0)
         hipLaunchKernelGGL(k_encode, dim3((unsigned)nb), dim3(kThreads), 0, st, in, n, block_off, nb, fixed, tbl, hdr, info,
                            out_off, ctl, out);
-    GZ_TRY(hipGetLastError());
+    PCABI_TRY(hipGetLastError());
     return 0;
-}
-
-void par_memcpy(void *dst, const void *src, size_t n) {
-    constexpr size_t kPiece = 8u << 20;
-    const int nt = (int)std::min<size_t>(4, n / kPiece);
-    if (nt <= 1) {
-        std::memcpy(dst, src, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) {
-        const size_t a = n * t / nt, e = n * (t + 1) / nt;
-        th.emplace_back([=] { std::memcpy((char *)dst + a, (const char *)src + a, e - a); });
-    }
-    for (auto &x : th) x.join();
 }
 
 // The host entry's staging slots: pinned and device buffers kept between calls (one device at a
 // time; a call on another device, or a larger pass, reallocates). One call runs at a time.
 struct Slot {
-    hipStream_t st = nullptr;
-    uint8_t *pin_in = nullptr, *pin_out = nullptr, *dev_in = nullptr, *dev_out = nullptr;
-    int64_t *pin_off = nullptr, *dev_off = nullptr, *pin_len = nullptr, *dev_len = nullptr;
-    void *scratch = nullptr;
+    PinBuf<> pin_in, pin_out;
+    PinBuf<int64_t> pin_off, pin_len;
+    DevBuf<> dev_in, dev_out;
+    DevBuf<int64_t> dev_off, dev_len;
+    DevBuf<> scratch;
     int64_t len = 0;
+    Stream st;   // the last member: the first to go
+    // f(buffer, elements) for every buffer of a pass of up to bytes / blocks, until one returns false
+    template <class F>
+    bool each(int64_t bytes, int64_t blocks, F f) {
+        const int64_t ob = std::max(bound(bytes, blocks), bgzf_bound(bytes, blocks, 0));
+        return f(pin_in, bytes + 16) && f(pin_out, ob) && f(pin_off, blocks + 1) && f(pin_len, 8) && f(dev_in, bytes + 16) &&
+               f(dev_out, ob) && f(dev_off, blocks + 1) && f(dev_len, 8) && f(scratch, scratch_bytes(blocks));
+    }
 };
 constexpr int kSlots = 3;
 struct Stage {
     int device = -1;
-    int64_t bytes = 0, blocks = 0;
     Slot s[kSlots];
     double t_copy_in = 0, t_sync = 0, t_copy_out = 0;
-} g_stage;
+};
+// kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
+// HIP runtime that may already have shut down
+Stage &g_stage = *new Stage;
 std::mutex g_stage_mu;
 
-void stage_free() {
-    if (g_stage.device < 0) return;
-    for (Slot &s : g_stage.s) {
-        if (s.st) (void)hipStreamDestroy(s.st);
-        if (s.pin_in) (void)hipHostFree(s.pin_in);
-        if (s.pin_out) (void)hipHostFree(s.pin_out);
-        if (s.pin_off) (void)hipHostFree(s.pin_off);
-        if (s.pin_len) (void)hipHostFree(s.pin_len);
-        if (s.dev_in) (void)hipFree(s.dev_in);
-        if (s.dev_out) (void)hipFree(s.dev_out);
-        if (s.dev_off) (void)hipFree(s.dev_off);
-        if (s.dev_len) (void)hipFree(s.dev_len);
-        if (s.scratch) (void)hipFree(s.scratch);
-        s = Slot();
-    }
-    g_stage.device = -1;
-    g_stage.bytes = g_stage.blocks = 0;
-}
-
+// Whether the kept buffers serve is read from the buffers themselves, so a reserve that failed half-way
+// is done again by the next call.
 int stage_reserve(int device, int64_t bytes, int64_t blocks) {
-    if (g_stage.device == device && g_stage.bytes >= bytes && g_stage.blocks >= blocks) return 0;
+    bool kept = g_stage.device == device;
+    for (Slot &s : g_stage.s) kept = kept && s.each(bytes, blocks, [](auto &b, int64_t n) { return holds(b, n); });
+    if (kept) return 0;
     if (g_stage.device >= 0) {
         (void)hipSetDevice(g_stage.device);
-        stage_free();
+        for (Slot &s : g_stage.s) {
+            s.st.release();
+            s = Slot();
+        }
     }
-    GZ_TRY(hipSetDevice(device));
+    PCABI_TRY(hipSetDevice(device));
     g_stage.device = device;
-    g_stage.bytes = bytes;
-    g_stage.blocks = blocks;
-    const size_t ob = (size_t)std::max(bound(bytes, blocks), bgzf_bound(bytes, blocks, 0));
-    for (Slot &s : g_stage.s) {
-        GZ_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-        GZ_TRY(hipHostMalloc((void **)&s.pin_in, (size_t)bytes + 16, hipHostMallocDefault));
-        GZ_TRY(hipHostMalloc((void **)&s.pin_out, ob, hipHostMallocDefault));
-        GZ_TRY(hipHostMalloc((void **)&s.pin_off, 8 * (size_t)(blocks + 1), hipHostMallocDefault));
-        GZ_TRY(hipHostMalloc((void **)&s.pin_len, 64, hipHostMallocDefault));
-        GZ_TRY(hipMalloc((void **)&s.dev_in, (size_t)bytes + 16));
-        GZ_TRY(hipMalloc((void **)&s.dev_out, ob));
-        GZ_TRY(hipMalloc((void **)&s.dev_off, 8 * (size_t)(blocks + 1)));
-        GZ_TRY(hipMalloc((void **)&s.dev_len, 64));
-        GZ_TRY(hipMalloc(&s.scratch, (size_t)scratch_bytes(blocks)));
-    }
-    return 0;
-}
-
-double now_s() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+    int rc = 0;
+    for (Slot &s : g_stage.s)
+        if (!rc && !(rc = s.st.create())) s.each(bytes, blocks, [&](auto &b, int64_t n) { return (rc = b.reserve(n, n)) == 0; });
+    return rc;
 }
 
 }  // namespace
@@ -659,8 +616,8 @@ static int64_t gzip_host_impl(int device, const uint8_t *in, int64_t n, const in
         max_bytes = std::max(max_bytes, byte_at(pass[p + 1]) - byte_at(pass[p]));
         max_blocks = std::max(max_blocks, pass[p + 1] - pass[p]);
     }
-    if (device < 0) GZ_TRY(hipGetDevice(&device));
-    GZ_TRY(hipSetDevice(device));
+    if (device < 0) PCABI_TRY(hipGetDevice(&device));
+    PCABI_TRY(hipSetDevice(device));
     if (int rc = stage_reserve(device, std::max<int64_t>(max_bytes, 1 << 16), std::max<int64_t>(max_blocks, 16))) return rc;
     g_stage.t_copy_in = g_stage.t_sync = g_stage.t_copy_out = 0;
     int64_t total = 0;
@@ -674,28 +631,28 @@ static int64_t gzip_host_impl(int device, const uint8_t *in, int64_t n, const in
             if (block_off)
                 for (int64_t b = b0; b <= b1; ++b) s.pin_off[b - b0] = block_off[b] - lo;
             g_stage.t_copy_in += now_s() - t0;
-            if (bytes > 0) GZ_TRY(hipMemcpyAsync(s.dev_in, s.pin_in, (size_t)bytes, hipMemcpyHostToDevice, s.st));
+            if (bytes > 0) PCABI_TRY(hipMemcpyAsync(s.dev_in, s.pin_in, (size_t)bytes, hipMemcpyHostToDevice, s.st));
             if (block_off)
-                GZ_TRY(hipMemcpyAsync(s.dev_off, s.pin_off, 8 * (size_t)(b1 - b0 + 1), hipMemcpyHostToDevice, s.st));
+                PCABI_TRY(hipMemcpyAsync(s.dev_off, s.pin_off, 8 * (size_t)(b1 - b0 + 1), hipMemcpyHostToDevice, s.st));
             if (int rc = launch(s.st, s.dev_in, bytes, block_off ? s.dev_off : nullptr, b1 - b0, fixed, member_blocks, hdr,
                                 s.dev_out, bgzf ? bgzf_bound(bytes, b1 - b0, 0) : bound(bytes, b1 - b0), s.dev_len,
                                 s.scratch))
                 return rc;
-            GZ_TRY(hipMemcpyAsync(s.pin_len, s.dev_len, 8, hipMemcpyDeviceToHost, s.st));
+            PCABI_TRY(hipMemcpyAsync(s.pin_len, s.dev_len, 8, hipMemcpyDeviceToHost, s.st));
         }
         if (i >= 1 && i - 1 < np) {   // stage B: the compressed bytes back
             Slot &s = g_stage.s[(i - 1) % kSlots];
             const double t0 = now_s();
-            GZ_TRY(hipStreamSynchronize(s.st));
+            PCABI_TRY(hipStreamSynchronize(s.st));
             g_stage.t_sync += now_s() - t0;
             s.len = *s.pin_len;
             if (s.len < 0) return fail(PCABI_E_ARG, "bad block list");
-            GZ_TRY(hipMemcpyAsync(s.pin_out, s.dev_out, (size_t)s.len, hipMemcpyDeviceToHost, s.st));
+            PCABI_TRY(hipMemcpyAsync(s.pin_out, s.dev_out, (size_t)s.len, hipMemcpyDeviceToHost, s.st));
         }
         if (i >= 2) {   // stage C: into the caller's buffer
             Slot &s = g_stage.s[(i - 2) % kSlots];
             double t0 = now_s();
-            GZ_TRY(hipStreamSynchronize(s.st));
+            PCABI_TRY(hipStreamSynchronize(s.st));
             g_stage.t_sync += now_s() - t0;
             t0 = now_s();
             fits = fits && total + s.len <= cap;

@@ -1,0 +1,183 @@
+// pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
+// pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
+// compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
+#pragma once
+
+#include <time.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/pcabi.h"
+
+namespace pcabi_bam {
+struct Layout;
+}
+
+namespace pcabi_internal {
+
+int fail(int code, const std::string &msg);   // pcabi_engine.hip: pcabi_last_error()
+
+inline void par_memcpy(void *dst, const void *src, size_t n) {
+    constexpr size_t kPiece = 8u << 20;
+    const int nt = (int)std::min<size_t>(4, n / kPiece);
+    if (nt <= 1) {
+        std::memcpy(dst, src, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) {
+        const size_t a = n * t / nt, e = n * (t + 1) / nt;
+        th.emplace_back([=] { std::memcpy((char *)dst + a, (const char *)src + a, e - a); });
+    }
+    for (auto &x : th) x.join();
+}
+
+inline double now_s() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// A buffer of T that frees itself: Mem::alloc(void **, bytes) returns 0 or a fail() code, Mem::free(void *)
+// releases. cap (in elements) is non-zero only while p is live, so "does it hold n" is a question to the
+// allocation itself. The device that must be current when memory goes is the holder's business.
+template <class Mem, class T = uint8_t>
+struct Owned {
+    T *p = nullptr;
+    int64_t cap = 0;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~Owned() { release(); }
+    void release() {
+        if (p) Mem::free(p);
+        p = nullptr, cap = 0;
+    }
+    // room for `need` elements: nothing when they fit, else the old block goes first and `want` (the
+    // caller's growth rule, >= need) are allocated; a failure leaves {nullptr, 0}
+    int reserve(int64_t need, int64_t want) {
+        if (need <= cap) return 0;
+        release();
+        void *q = nullptr;
+        if (int rc = Mem::alloc(&q, (size_t)want * sizeof(T))) return rc;
+        p = (T *)q, cap = want;
+        return 0;
+    }
+    operator T *() const { return p; }
+};
+
+// may kept buffers serve a call that needs these sizes? holds(owner, need, owner, need, ...)
+inline bool holds() { return true; }
+template <class O, class... Rest>
+bool holds(const O &o, int64_t need, const Rest &...rest) {
+    return need <= o.cap && holds(rest...);
+}
+
+#ifdef __HIPCC__
+#define PCABI_TRY(expr)                                                                     \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            return pcabi_internal::fail(PCABI_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+struct DevAlloc {
+    static int alloc(void **p, size_t n) {
+        PCABI_TRY(hipMalloc(p, n));
+        return 0;
+    }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinAlloc {
+    static int alloc(void **p, size_t n) {
+        PCABI_TRY(hipHostMalloc(p, n, hipHostMallocDefault));
+        return 0;
+    }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <class T = uint8_t>
+using DevBuf = Owned<DevAlloc, T>;
+template <class T = uint8_t>
+using PinBuf = Owned<PinAlloc, T>;
+
+// a non-blocking stream, synchronised and destroyed when it goes
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&o) noexcept {
+        if (this != &o) {
+            release();
+            s = o.s;
+            o.s = nullptr;
+        }
+        return *this;
+    }
+    ~Stream() { release(); }
+    int create() {
+        release();
+        PCABI_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return 0;
+    }
+    void release() {
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+        s = nullptr;
+    }
+    operator hipStream_t() const { return s; }
+};
+#endif
+
+// ---- pcabi_inflate.hip ---------------------------------------------------------------------------
+std::vector<int64_t> gunzip_passes(const int64_t *out_off, int64_t m0, int64_t m1, int64_t chunk);
+int64_t gunzip_chunk_bytes();
+int gunzip_group_async(void *stream, const uint8_t *z, const int64_t *in_off, const int64_t *out_off, int64_t m0,
+                       int64_t m1, uint8_t *pin_in, int64_t *pin_off, uint8_t *dev_in, int64_t *dev_off,
+                       uint8_t *dev_out, int32_t *dev_status, uint8_t *pin_out, int32_t *pin_status);
+int gunzip_group_check(const int32_t *pin_status, const int64_t *in_off, int64_t m0, int64_t m1);
+// the device source of a block-gzipped input
+struct GunzipReader;
+int gunzip_reader_open(const uint8_t *z, int64_t n, int device, GunzipReader **out);
+int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room);
+int64_t gunzip_reader_take(GunzipReader *g, const uint8_t **host, const uint8_t **dev, void **stream);
+void gunzip_reader_unread(GunzipReader *g);
+int gunzip_reader_device(const GunzipReader *g);
+int64_t gunzip_reader_total(const GunzipReader *g);
+void gunzip_reader_close(GunzipReader *g);
+
+// ---- pcabi_bam.hip -------------------------------------------------------------------------------
+// device-event spans of the BAM timing tool: no-ops unless profiling is on
+bool prof_on();
+void *prof_begin(void *stream, int kind);
+void prof_end(void *stream, void *span);
+// the device half of a BAM reader
+struct BamDev;
+int bam_dev_open(int device, BamDev **out);
+void bam_dev_close(BamDev *b);
+int bam_dev_append(BamDev *b, int64_t keep_from, const uint8_t *src, int64_t n, void *stream);
+int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const pcabi_bam::Layout &lay,
+                   const uint8_t **seq, const uint8_t **qual, const uint8_t **codes);
+// the device half of the BAM writer: the stream packed and compressed on the device; sink receives its
+// members (pinned memory, valid inside the call)
+int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
+                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink);
+
+}  // namespace pcabi_internal

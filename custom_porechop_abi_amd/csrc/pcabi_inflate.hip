@@ -18,29 +18,16 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/pcabi.h"
 #include "pcabi_crc.h"
+#include "pcabi_hostdev.h"
 #include "pcabi_inflate.h"
 
-namespace pcabi_internal {
-int fail(int code, const std::string &msg);
-// device-event spans of the BAM timing tool (pcabi_bam.hip): no-ops unless profiling is on
-bool prof_on();
-void *prof_begin(void *stream, int kind);
-void prof_end(void *stream, void *span);
-}
-using pcabi_internal::fail;
+using namespace pcabi_internal;
 using namespace pcabi_inflate;
 using namespace pcabi_crc;
-
-#define GUZ_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return fail(PCABI_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -147,102 +134,67 @@ int64_t g_chunk_bytes = kDefaultChunk;
 int launch(hipStream_t st, const uint8_t *z, int64_t n, const int64_t *in_off, const int64_t *out_off, int64_t nm,
            uint8_t *out, int64_t out_cap, int32_t *status) {
     if (nm > 0) hipLaunchKernelGGL(k_inflate, dim3((unsigned)nm), dim3(kWave), 0, st, z, n, in_off, out_off, out, out_cap, status);
-    GUZ_TRY(hipGetLastError());
+    PCABI_TRY(hipGetLastError());
     return 0;
-}
-
-void par_memcpy(void *dst, const void *src, size_t n) {
-    constexpr size_t kPiece = 8u << 20;
-    const int nt = (int)std::min<size_t>(4, n / kPiece);
-    if (nt <= 1) {
-        std::memcpy(dst, src, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) {
-        const size_t a = n * t / nt, e = n * (t + 1) / nt;
-        th.emplace_back([=] { std::memcpy((char *)dst + a, (const char *)src + a, e - a); });
-    }
-    for (auto &x : th) x.join();
 }
 
 // The host entry's staging slots: pinned and device buffers kept between calls (one device at a
 // time; a call on another device, or a larger pass, reallocates). One call runs at a time.
 struct Slot {
-    hipStream_t st = nullptr;
-    uint8_t *pin_in = nullptr, *pin_out = nullptr, *dev_in = nullptr, *dev_out = nullptr;
-    int64_t *pin_off = nullptr, *dev_off = nullptr;   // in_off[members + 1], then out_off[members + 1]
-    int32_t *pin_status = nullptr, *dev_status = nullptr;
+    PinBuf<> pin_in, pin_out;
+    PinBuf<int64_t> pin_off;   // in_off[members + 1], then out_off[members + 1]
+    PinBuf<int32_t> pin_status;
+    DevBuf<> dev_in, dev_out;
+    DevBuf<int64_t> dev_off;
+    DevBuf<int32_t> dev_status;
     int64_t m0 = 0, m1 = 0;
+    Stream st;   // the last member: the first to go
+    // f(buffer, elements) for every buffer of groups of up to in_bytes / out_bytes / members, until one
+    // returns false
+    template <class F>
+    bool each(int64_t in_bytes, int64_t out_bytes, int64_t members, F f) {
+        return f(pin_in, in_bytes + 16) && f(pin_out, out_bytes + 16) && f(pin_off, 2 * (members + 1)) &&
+               f(pin_status, members + 4) && f(dev_in, in_bytes + 16) && f(dev_out, out_bytes + 16) &&
+               f(dev_off, 2 * (members + 1)) && f(dev_status, members + 4);
+    }
 };
 constexpr int kSlots = 2;
 struct Stage {
     int device = -1;
-    int64_t in_bytes = 0, out_bytes = 0, members = 0;
     Slot s[kSlots];
     double t_copy_in = 0, t_sync = 0, t_copy_out = 0;
-} g_stage;
+};
+// kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
+// HIP runtime that may already have shut down
+Stage &g_stage = *new Stage;
 std::mutex g_stage_mu;
-
-void slot_free(Slot &s) {
-    if (s.st) {
-        (void)hipStreamSynchronize(s.st);
-        (void)hipStreamDestroy(s.st);
-    }
-    if (s.pin_in) (void)hipHostFree(s.pin_in);
-    if (s.pin_out) (void)hipHostFree(s.pin_out);
-    if (s.pin_off) (void)hipHostFree(s.pin_off);
-    if (s.pin_status) (void)hipHostFree(s.pin_status);
-    if (s.dev_in) (void)hipFree(s.dev_in);
-    if (s.dev_out) (void)hipFree(s.dev_out);
-    if (s.dev_off) (void)hipFree(s.dev_off);
-    if (s.dev_status) (void)hipFree(s.dev_status);
-    s = Slot();
-}
 
 // a slot's stream and buffers for groups of up to in_bytes / out_bytes / members (current device)
 int slot_alloc(Slot &s, int64_t in_bytes, int64_t out_bytes, int64_t members) {
-    GUZ_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-    GUZ_TRY(hipHostMalloc((void **)&s.pin_in, (size_t)in_bytes + 16, hipHostMallocDefault));
-    GUZ_TRY(hipHostMalloc((void **)&s.pin_out, (size_t)out_bytes + 16, hipHostMallocDefault));
-    GUZ_TRY(hipHostMalloc((void **)&s.pin_off, 16 * (size_t)(members + 1), hipHostMallocDefault));
-    GUZ_TRY(hipHostMalloc((void **)&s.pin_status, 4 * (size_t)members + 16, hipHostMallocDefault));
-    GUZ_TRY(hipMalloc((void **)&s.dev_in, (size_t)in_bytes + 16));
-    GUZ_TRY(hipMalloc((void **)&s.dev_out, (size_t)out_bytes + 16));
-    GUZ_TRY(hipMalloc((void **)&s.dev_off, 16 * (size_t)(members + 1)));
-    GUZ_TRY(hipMalloc((void **)&s.dev_status, 4 * (size_t)members + 16));
-    return 0;
+    int rc = s.st.create();
+    if (!rc) s.each(in_bytes, out_bytes, members, [&](auto &b, int64_t n) { return (rc = b.reserve(n, n)) == 0; });
+    return rc;
 }
 
-void stage_free() {
-    if (g_stage.device < 0) return;
-    for (Slot &s : g_stage.s) slot_free(s);
-    g_stage.device = -1;
-    g_stage.in_bytes = g_stage.out_bytes = g_stage.members = 0;
-}
-
+// Whether the kept buffers serve is read from the buffers themselves, so a reserve that failed half-way
+// is done again by the next call.
 int stage_reserve(int device, int64_t in_bytes, int64_t out_bytes, int64_t members) {
-    if (g_stage.device == device && g_stage.in_bytes >= in_bytes && g_stage.out_bytes >= out_bytes &&
-        g_stage.members >= members)
-        return 0;
+    bool kept = g_stage.device == device;
+    for (Slot &s : g_stage.s)
+        kept = kept && s.each(in_bytes, out_bytes, members, [](auto &b, int64_t n) { return holds(b, n); });
+    if (kept) return 0;
     if (g_stage.device >= 0) {
         (void)hipSetDevice(g_stage.device);
-        stage_free();
+        for (Slot &s : g_stage.s) {
+            s.st.release();
+            s = Slot();
+        }
     }
-    GUZ_TRY(hipSetDevice(device));
+    PCABI_TRY(hipSetDevice(device));
     g_stage.device = device;
-    g_stage.in_bytes = in_bytes;
-    g_stage.out_bytes = out_bytes;
-    g_stage.members = members;
     for (Slot &s : g_stage.s)
         if (int rc = slot_alloc(s, in_bytes, out_bytes, members)) return rc;
     return 0;
-}
-
-double now_s() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
 }  // namespace
@@ -279,13 +231,13 @@ int gunzip_group_async(void *stream, const uint8_t *z, const int64_t *in_off, co
     }
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 2) : nullptr;
-    if (bytes > 0) GUZ_TRY(hipMemcpyAsync(dev_in, pin_in, (size_t)bytes, hipMemcpyHostToDevice, st));
-    GUZ_TRY(hipMemcpyAsync(dev_off, pin_off, 16 * (size_t)(nm + 1), hipMemcpyHostToDevice, st));
+    if (bytes > 0) PCABI_TRY(hipMemcpyAsync(dev_in, pin_in, (size_t)bytes, hipMemcpyHostToDevice, st));
+    PCABI_TRY(hipMemcpyAsync(dev_off, pin_off, 16 * (size_t)(nm + 1), hipMemcpyHostToDevice, st));
     if (prof) prof_end(st, sp), sp = prof_begin(st, 0);
     if (int rc = launch(st, dev_in, bytes, dev_off, dev_off + nm + 1, nm, dev_out, obytes, dev_status)) return rc;
     if (prof) prof_end(st, sp), sp = prof_begin(st, 3);
-    if (nm > 0) GUZ_TRY(hipMemcpyAsync(pin_status, dev_status, 4 * (size_t)nm, hipMemcpyDeviceToHost, st));
-    if (obytes > 0) GUZ_TRY(hipMemcpyAsync(pin_out, dev_out, (size_t)obytes, hipMemcpyDeviceToHost, st));
+    if (nm > 0) PCABI_TRY(hipMemcpyAsync(pin_status, dev_status, 4 * (size_t)nm, hipMemcpyDeviceToHost, st));
+    if (obytes > 0) PCABI_TRY(hipMemcpyAsync(pin_out, dev_out, (size_t)obytes, hipMemcpyDeviceToHost, st));
     if (prof) prof_end(st, sp);
     return 0;
 }
@@ -316,7 +268,6 @@ struct GunzipReader {
 
 static void reader_free(GunzipReader *g) {
     (void)hipSetDevice(g->device);
-    for (Slot &s : g->s) slot_free(s);
     delete g;
 }
 
@@ -329,7 +280,7 @@ static int reader_launch(GunzipReader *g, int64_t p) {
 }
 
 static int reader_alloc(GunzipReader *g, int64_t max_in, int64_t max_out, int64_t max_m) {
-    GUZ_TRY(hipSetDevice(g->device));
+    PCABI_TRY(hipSetDevice(g->device));
     for (Slot &s : g->s)
         if (int rc = slot_alloc(s, max_in, max_out, max_m)) return rc;
     return 0;
@@ -382,10 +333,10 @@ int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room) {
         }
         if (g->pending) return fail(g->pending, g->pending_msg);
         if (g->consume >= g->np) return 0;
-        GUZ_TRY(hipSetDevice(g->device));
+        PCABI_TRY(hipSetDevice(g->device));
         const int64_t p = g->consume++;
         Slot &s = g->s[p % kSlots];
-        GUZ_TRY(hipStreamSynchronize(s.st));
+        PCABI_TRY(hipStreamSynchronize(s.st));
         int64_t good = s.m1;
         for (int64_t m = s.m0; m < s.m1; ++m)
             if (s.pin_status[m - s.m0] != 0) {
@@ -492,8 +443,8 @@ int64_t pcabi_gunzip_host(int device, const uint8_t *z, int64_t n, uint8_t *out,
         max_out = std::max(max_out, out_off[pass[p + 1]] - out_off[pass[p]]);
         max_m = std::max(max_m, pass[p + 1] - pass[p]);
     }
-    if (device < 0) GUZ_TRY(hipGetDevice(&device));
-    GUZ_TRY(hipSetDevice(device));
+    if (device < 0) PCABI_TRY(hipGetDevice(&device));
+    PCABI_TRY(hipSetDevice(device));
     if (int rc = stage_reserve(device, std::max<int64_t>(max_in, 1 << 16), std::max<int64_t>(max_out, 1 << 16),
                                std::max<int64_t>(max_m, 16)))
         return rc;
@@ -514,7 +465,7 @@ int64_t pcabi_gunzip_host(int device, const uint8_t *z, int64_t n, uint8_t *out,
         if (i >= 1) {   // stage B: into the caller's buffer
             Slot &s = g_stage.s[(i - 1) % kSlots];
             double t0 = now_s();
-            GUZ_TRY(hipStreamSynchronize(s.st));
+            PCABI_TRY(hipStreamSynchronize(s.st));
             g_stage.t_sync += now_s() - t0;
             if (!rc_all) rc_all = pcabi_internal::gunzip_group_check(s.pin_status, in_off.data(), s.m0, s.m1);
             t0 = now_s();

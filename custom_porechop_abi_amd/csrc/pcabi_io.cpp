@@ -56,11 +56,10 @@
 #include "../../include/pcabi.h"
 #include "pcabi_bam.h"
 #include "pcabi_deflate.h"
+#include "pcabi_hostdev.h"
 
-namespace pcabi_internal {
-int fail(int code, const std::string &msg);   // pcabi_engine.hip: pcabi_last_error()
-}
 using pcabi_internal::fail;
+using pcabi_internal::now_s;
 
 namespace {
 
@@ -81,25 +80,6 @@ const bool g_dna5_init = [] {
 }();
 
 }  // namespace
-
-namespace pcabi_internal {
-// the device source of a block-gzipped input (csrc/pcabi_inflate.hip)
-struct GunzipReader;
-int gunzip_reader_open(const uint8_t *z, int64_t n, int device, GunzipReader **out);
-int64_t gunzip_reader_read(GunzipReader *g, char *dst, int64_t room);
-void gunzip_reader_close(GunzipReader *g);
-int64_t gunzip_reader_take(GunzipReader *g, const uint8_t **host, const uint8_t **dev, void **stream);
-void gunzip_reader_unread(GunzipReader *g);
-int gunzip_reader_device(const GunzipReader *g);
-int64_t gunzip_reader_total(const GunzipReader *g);
-// the device half of a BAM reader (csrc/pcabi_bam.hip)
-struct BamDev;
-int bam_dev_open(int device, BamDev **out);
-void bam_dev_close(BamDev *b);
-int bam_dev_append(BamDev *b, int64_t keep_from, const uint8_t *src, int64_t n, void *stream);
-int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const pcabi_bam::Layout &lay,
-                   const uint8_t **seq, const uint8_t **qual, const uint8_t **codes);
-}  // namespace pcabi_internal
 
 // A BAM input's state. win[0, end) is a window of the inflated bytes (on the device path mirrored there,
 // pcabi_bam.hip BamDev): the record chain is walked from `at`, whole records are unpacked into the
@@ -1567,8 +1547,31 @@ bool read_parts(const WriteArgs &w, int64_t i, std::vector<std::pair<int64_t, in
 // seconds the calling thread's last pcabi_reads_write* spent laying the records out (sizing, fill,
 // block planning), compressing (gz = 2: pcabi_gzip_host) and writing the file
 static thread_local double g_write_times[3] = {0, 0, 0};
-static double wall_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+
+// p[0, n) to fd in write() calls of at most 256 MiB; false when one fails
+static bool write_all(int fd, const void *p, size_t n) {
+    for (size_t k = 0; k < n;) {
+        const ssize_t w = ::write(fd, (const char *)p + k, std::min<size_t>(n - k, 256u << 20));
+        if (w < 0) {
+            if (errno == EINTR) continue;
+            return false;
+        }
+        k += (size_t)w;
+    }
+    return true;
+}
+
+// fn(t) for t in [0, threads), each on a thread of its own (inline for one): a range of the work by
+// index, or items taken from a shared counter
+template <class F>
+static void fan_out(int threads, F &&fn) {
+    if (threads <= 1) {
+        fn(0);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; ++t) th.emplace_back(fn, t);
+    for (auto &x : th) x.join();
 }
 
 static int reads_write_impl(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
@@ -1604,37 +1607,16 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
     // (e2e writer 8.1 GB/s against 11.9 for one contiguous buffer, bench write_probe).
     int64_t emitted = 0;
     g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
-    const double t_begin = wall_s();
+    const double t_begin = now_s();
     const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
     // gz = 2: the same buffer, cut into blocks at line ends by the thread that filled each range
     // (pcabi_deflate.h plan_blocks), compressed on the device and written as gzip members.
     std::vector<char, NoInit<char>> out;
     std::vector<std::vector<int64_t>> ends((size_t)std::max(nt, 1));
-    auto write_all = [&](const char *p, size_t n) {
-        size_t k = 0;
-        while (o.ok && k < n) {
-            const ssize_t w = ::write(o.fd, p + k, std::min<size_t>(n - k, 256u << 20));
-            if (w < 0) {
-                if (errno == EINTR) continue;
-                o.ok = false;
-                break;
-            }
-            k += (size_t)w;
-        }
-    };
     if (o.fd >= 0 && b->n > 0) {
         std::vector<int64_t> lo((size_t)nt + 1), bytes((size_t)nt + 1, 0), emit((size_t)nt, 0);
         for (int t = 0; t <= nt; ++t) lo[(size_t)t] = b->n * t / nt;
-        auto par = [&](auto &&fn) {
-            if (nt <= 1) {
-                fn(0);
-                return;
-            }
-            std::vector<std::thread> th;
-            for (int t = 0; t < nt; ++t) th.emplace_back(fn, t);
-            for (auto &x : th) x.join();
-        };
-        par([&](int t) {
+        fan_out(nt, [&](int t) {
             std::vector<std::pair<int64_t, int64_t>> rg;
             CountSink c;
             for (int64_t i = lo[(size_t)t]; i < lo[(size_t)t + 1]; ++i) format(i, c, rg);
@@ -1642,7 +1624,7 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
         });
         for (int t = 0; t < nt; ++t) bytes[(size_t)t + 1] += bytes[(size_t)t];
         out.resize((size_t)bytes[(size_t)nt]);
-        par([&](int t) {
+        fan_out(nt, [&](int t) {
             std::vector<std::pair<int64_t, int64_t>> rg;
             MemSink m{out.data() + bytes[(size_t)t]};
             int64_t e = 0;
@@ -1654,11 +1636,11 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
                                            [&](int64_t end) { ends[(size_t)t].push_back(end); });
         });
         for (int t = 0; t < nt; ++t) emitted += emit[(size_t)t];
-        g_write_times[0] = wall_s() - t_begin;
+        g_write_times[0] = now_s() - t_begin;
         if (gz != 2) {
-            const double t0 = wall_s();
-            write_all(out.data(), out.size());
-            g_write_times[2] = wall_s() - t0;
+            const double t0 = now_s();
+            o.ok = o.ok && write_all(o.fd, out.data(), out.size());
+            g_write_times[2] = now_s() - t0;
         }
     } else {
         std::vector<std::pair<int64_t, int64_t>> rg;
@@ -1671,19 +1653,19 @@ static int reads_write_impl(const pcabi_reads *b, const char *path, int append, 
         std::vector<uint8_t, NoInit<uint8_t>> z;
         z.resize((size_t)(bgzf ? pcabi_bgzf_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1), 0)
                                : pcabi_gzip_bound((int64_t)out.size(), std::max<int64_t>(nblk, 1))));
-        const double t0 = wall_s();
+        const double t0 = now_s();
         const int64_t zn = bgzf ? pcabi_bgzf_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
                                                   block_off.data(), nblk, 0, z.data(), (int64_t)z.size())
                                 : pcabi_gzip_host(gzip_device, (const uint8_t *)out.data(), (int64_t)out.size(),
                                                   block_off.data(), nblk, z.data(), (int64_t)z.size());
-        g_write_times[1] = wall_s() - t0;
+        g_write_times[1] = now_s() - t0;
         if (zn < 0 || zn > (int64_t)z.size()) {
             ::close(o.fd);
             return zn < 0 ? (int)zn : fail(PCABI_E_ARG, "gzip capacity bound exceeded");
         }
-        const double t1 = wall_s();
-        write_all((const char *)z.data(), (size_t)zn);
-        g_write_times[2] = wall_s() - t1;
+        const double t1 = now_s();
+        o.ok = o.ok && write_all(o.fd, z.data(), (size_t)zn);
+        g_write_times[2] = now_s() - t1;
     }
     o.flush();
     const bool ok = o.ok;
@@ -1717,14 +1699,6 @@ extern "C" void pcabi_reads_write_last_times(double *layout, double *compress, d
 }
 
 // ---- BAM writer ------------------------------------------------------------------------------
-namespace pcabi_internal {
-// the device half (csrc/pcabi_bam.hip): the stream packed and compressed on the device; sink receives its
-// members (pinned memory, valid inside the call)
-int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
-                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
-                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink);
-}
-
 namespace {
 
 // One BGZF member of data[0, n) (n <= 65280) appended to z: zlib raw deflate, stored when that fails to fit.
@@ -1765,7 +1739,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
         return fail(PCABI_E_ARG, "bad arguments");
     if (std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "BAM output goes to files, not stdout");
     g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
-    const double t_begin = wall_s();
+    const double t_begin = now_s();
     const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
     const bool have_aux = keep_aux && !b->aux_off.empty();
     const bool no_qual = b->type == PCABI_FASTA;
@@ -1774,16 +1748,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
     std::vector<std::vector<uint8_t>> t_side((size_t)nt);
     std::vector<int64_t> t_emit((size_t)nt, 0);
-    auto par = [&](auto &&fn) {
-        if (nt <= 1) {
-            fn(0);
-            return;
-        }
-        std::vector<std::thread> th;
-        for (int t = 0; t < nt; ++t) th.emplace_back(fn, t);
-        for (auto &x : th) x.join();
-    };
-    par([&](int t) {
+    fan_out(nt, [&](int t) {
         std::vector<std::pair<int64_t, int64_t>> rg;
         std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
         std::vector<uint8_t> &side = t_side[(size_t)t];
@@ -1852,33 +1817,25 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
     if (fd < 0) return fail(PCABI_E_ARG, std::string("could not write ") + path);
     bool ok = true;
-    auto write_all = [&](const uint8_t *p, int64_t n) {
-        const double t1 = wall_s();
-        for (size_t k = 0; ok && k < (size_t)n;) {
-            const ssize_t w = ::write(fd, p + k, std::min<size_t>((size_t)n - k, 256u << 20));
-            if (w < 0) {
-                if (errno == EINTR) continue;
-                ok = false;
-                break;
-            }
-            k += (size_t)w;
-        }
-        g_write_times[2] += wall_s() - t1;
+    auto write_timed = [&](const uint8_t *p, int64_t n) {
+        const double t1 = now_s();
+        ok = ok && write_all(fd, p, (size_t)n);
+        g_write_times[2] += now_s() - t1;
     };
     if (device >= 0) {
-        g_write_times[0] = wall_s() - t_begin;
-        const double t0 = wall_s();
+        g_write_times[0] = now_s() - t_begin;
+        const double t0 = now_s();
         if (stream_n > 0) {
             const int64_t zn = pcabi_internal::bam_write_dev(device, head.data(), (int64_t)head.size(), (const uint8_t *)b->seq.data(),
                                                              seq_n, (const uint8_t *)b->qual.data(), qual_n, side.data(),
                                                              (int64_t)side.size(), parts.data(), (int64_t)parts.size(), lay.tiles,
-                                                             stream_n, write_all);
+                                                             stream_n, write_timed);
             if (zn < 0) {
                 ::close(fd);
                 return (int)zn;
             }
         }
-        g_write_times[1] = wall_s() - t0 - g_write_times[2];
+        g_write_times[1] = now_s() - t0 - g_write_times[2];
     } else {
         std::vector<uint8_t, NoInit<uint8_t>> stream;
         stream.resize((size_t)stream_n);
@@ -1886,39 +1843,28 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
         const int64_t np = (int64_t)parts.size();
         const int pt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, stream_n >> 20));
         std::atomic<int64_t> next{0};
-        auto pool = [&](int threads, auto &&fn) {
-            if (threads <= 1) {
-                fn();
-                return;
-            }
-            std::vector<std::thread> th;
-            for (int t = 0; t < threads; ++t) th.emplace_back(fn);
-            for (auto &x : th) x.join();
-        };
-        pool(pt, [&] {
+        fan_out(pt, [&](int) {
             for (int64_t i0; (i0 = next.fetch_add(256)) < np;)
                 for (int64_t i = i0; i < std::min(np, i0 + 256); ++i)
                     pack_part(parts[(size_t)i], (const uint8_t *)b->seq.data(), (const uint8_t *)b->qual.data(), side.data(),
                               stream.data());
         });
-        g_write_times[0] = wall_s() - t_begin;
-        const double t0 = wall_s();
+        g_write_times[0] = now_s() - t_begin;
+        const double t0 = now_s();
         const int64_t block = PCABI_BGZF_BLOCK_CAP, nm = (stream_n + block - 1) / block;
         const int zt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, nm / 4));
         std::vector<std::vector<uint8_t>> zs((size_t)zt);
         std::atomic<bool> zok{true};
-        std::atomic<int> slot{0};
-        pool(zt, [&] {
-            const int t = slot.fetch_add(1);
+        fan_out(zt, [&](int t) {
             for (int64_t m = nm * t / zt; m < nm * (t + 1) / zt; ++m)
                 if (!bgzf_member(stream.data() + m * block, (size_t)std::min(block, stream_n - m * block), zs[(size_t)t])) zok = false;
         });
-        g_write_times[1] = wall_s() - t0;
+        g_write_times[1] = now_s() - t0;
         if (!zok) {
             ::close(fd);
             return fail(PCABI_E_ARG, "zlib failed on a BGZF member");
         }
-        for (const auto &v : zs) write_all(v.data(), (int64_t)v.size());
+        for (const auto &v : zs) write_timed(v.data(), (int64_t)v.size());
     }
     ok = (::close(fd) == 0) && ok;
     if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
