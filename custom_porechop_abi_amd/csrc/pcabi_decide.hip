@@ -28,6 +28,7 @@ __global__ __launch_bounds__(256) void k_flag_write(const uint8_t *flag, int32_t
                                                     const unsigned long long *off, int32_t *out, int64_t cap) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n_read) return;
+    if (off[n_read] > (unsigned long long)cap) return;   // the count does not fit: nothing is written
     int64_t k = (int64_t)off[r];
     for (int32_t a = 0; a < n_adp; ++a) {
         const int64_t i = (int64_t)a * n_read + r;

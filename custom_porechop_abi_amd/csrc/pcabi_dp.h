@@ -192,15 +192,23 @@ PCABI_HD int compat_flag(const Result &r, int n, int en_match) {
 // double: d = (100.0*m)/l (IEEE, as in alignment.cpp:82,89), round d*1e6 to an integer with
 // round-half-even on its EXACT value (fma residual), then q/1e6 correctly rounded -- which is
 // what both printf and Python's float() do. l == 0 -> NaN (the reference's "-nan").
+// The tie test must not subtract from p: device code is compiled with -ffp-contract=fast, which
+// fuses `d * 1e6 - k` into one fma of the EXACT product, and p's landing on a tie is then never
+// seen (the first length that reaches it is 64000 = 2^9 5^3; tools/pid6_ties.c lists the pairs).
+// Here p only enters floor, rint and a compare, the adds have no product operand, and the one
+// fma is explicit: no contraction setting of hipcc, clang or g++ changes the result.
 PCABI_HD double pid6(int m, int l) {
     if (l == 0) return __builtin_nan("");
     const double d = (100.0 * (double)m) / (double)l;
     const double p = d * 1e6;
     const double e = __builtin_fma(d, 1e6, -p);   // d*1e6 == p + e exactly
     double k = __builtin_rint(p);                 // half-even on p
-    const double f = p - k;                       // exact
-    if (f == 0.5 && e > 0.0) k += 1.0;
-    else if (f == -0.5 && e < 0.0) k -= 1.0;
+    const double t = __builtin_floor(p);
+    const double h = t + 0.5;                     // exact below 2^52; above, h == t (or t + 1 != p)
+    if (p == h && h != t) {                       // p rounded onto a tie: the exact product decides
+        if (e > 0.0) k = t + 1.0;
+        else if (e < 0.0) k = t;
+    }
     return k / 1e6;
 }
 

@@ -1108,15 +1108,20 @@ __global__ __launch_bounds__(256) void k_round_hits(const int32_t *hb, int64_t n
 }
 
 // The reads with their end adapters trimmed (nanopore_read.py:44-49,
-// get_seq_with_start_end_adapters_trimmed): view = [start_trim, len - end_trim), empty when the
-// trims meet.
+// get_seq_with_start_end_adapters_trimmed): the slice seq[start_trim : len - end_trim] with Python's
+// rules, as trimmed_bounds (porechop_abi.py) gives it on the host -- a negative stop (an end trim
+// longer than the read: a read shorter than end_size) counts from the end, both ends are clipped,
+// and the view is empty when they meet.
 __global__ __launch_bounds__(256) void k_trim_views(const int64_t *read_off, const int32_t *read_len,
                                                     const int32_t *start_trim, const int32_t *end_trim, int64_t n,
                                                     int64_t *view_off, int32_t *view_len) {
     for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) {
-        const int32_t st = start_trim[k];
+        const int64_t len = read_len[k], st = start_trim[k];
+        int64_t stop = len - end_trim[k];
+        if (stop < 0) stop += len;
+        stop = min(max(stop, (int64_t)0), len);
         view_off[k] = read_off[k] + st;
-        view_len[k] = max(read_len[k] - st - end_trim[k], 0);
+        view_len[k] = (int32_t)max(stop - min(st, len), (int64_t)0);
     }
 }
 

@@ -301,7 +301,11 @@ int pcabi_stream_side_streams(void *stream, int on);
  * Identities are compared exactly as the reference does after its text round trip
  * (alignment.cpp:118-119 prints "%f", nanopore_read.py:497-498 parses it back): the device
  * rounds 100*m/l to 6 decimals with round-half-even on the exact double, then to the nearest
- * double (pcabi::pid6, checked against Python's '%f' in tests/).
+ * double (pcabi::pid6). Python's '%f' pins both builds of it: the host build in
+ * tests/test_abi.py::test_pid6_host_exact and tests/test_dp_core_cpu.py::
+ * test_pid6_matches_text_round_trip, the device build bit for bit in tests/test_gpu_epilogues.py
+ * (test_device_pid6_grid, test_device_pid6_ties), each over the lengths whose ties only the exact
+ * product decides (64000, 128000, ...).
  * Writes start_trim[n_read], end_trim[n_read] (amounts, same integers as
  * NanoporeRead.start_trim_amount / end_trim_amount) and, when non-NULL, per-pair
  * "alignment recorded" flags (uint8, same layout as the results).
@@ -314,9 +318,11 @@ int pcabi_end_trim_dev(const int32_t *start_res, int64_t start_stride, int32_t n
 
 /*
  * The reads with their end adapters trimmed, on the device (nanopore_read.py:44-49,
- * get_seq_with_start_end_adapters_trimmed): view_off = read_off + start_trim, view_len =
- * max(read_len - start_trim - end_trim, 0) -- the middle scan's windows straight from
- * pcabi_end_trim_dev's amounts, with no host round trip. Async on `stream`.
+ * get_seq_with_start_end_adapters_trimmed): view_off = read_off + start_trim, view_len = the
+ * length of Python's slice seq[start_trim : read_len - end_trim] -- read_len - start_trim -
+ * end_trim while the trims fit; a negative stop (end_trim > read_len) counts from the end, both
+ * ends are clipped to the read, never below 0 -- the middle scan's windows straight from
+ * pcabi_end_trim_dev's amounts, with no host round trip. Trims are >= 0. Async on `stream`.
  */
 int pcabi_trim_views_dev(const int64_t *read_off, const int32_t *read_len, const int32_t *start_trim,
                          const int32_t *end_trim, int64_t n_read, int64_t *view_off, int32_t *view_len, void *stream);
@@ -340,7 +346,8 @@ int pcabi_trim_views_dev(const int64_t *read_off, const int32_t *read_len, const
  * The prepared adapter tables are kept per device between calls with the same adapters and scoring.
  *   pcabi_flag_list_dev : the list of one side from device pointers (async on `stream`): flagged
  *                         pairs (k_end_trim's flags, layout of pcabi_end_trim_dev) of a result
- *                         block -> out (7 rows x cap, as above), *n_out (device uint64) = the count.
+ *                         block -> out (7 rows x cap, as above), *n_out (device uint64) = the count;
+ *                         when the count exceeds cap, out is not written.
  */
 int pcabi_end_decisions_host(int device, const uint8_t *codes, int64_t codes_len, const int64_t *s_off,
                              const int32_t *s_len, const int64_t *e_off, const int32_t *e_len, int64_t n_read,

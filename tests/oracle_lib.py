@@ -5,6 +5,8 @@ import subprocess
 
 import numpy as np
 
+from tests.identity_ref import ref_pid6
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, 'oracle', 'liboracle.so')
 
@@ -100,7 +102,6 @@ def align_windows(windows, adapter_seqs, scoring, pairs=None, device=0):
 def first_hits_windows(windows, adapter_seqs, scoring, threshold, device=0):
     """Drop-in for custom_porechop_abi_amd.engine.first_hits computed by the oracle (CPU): the
     first adapter (list order) whose full identity is not below threshold, per window."""
-    from custom_porechop_abi_amd.engine import pid6
     n_win = len(windows[2])
     out = np.zeros((5, n_win), np.int32)
     out[0] = -1
@@ -109,7 +110,7 @@ def first_hits_windows(windows, adapter_seqs, scoring, threshold, device=0):
         return out
     res = align_windows(windows, adapter_seqs, scoring)
     n_adp = len(adapter_seqs)
-    full = np.where(res[0] == -1, 0.0, pid6(res[5], res[7])).reshape(n_adp, n_win)
+    full = np.where(res[0] == -1, 0.0, ref_pid6(res[5], res[7])).reshape(n_adp, n_win)
     strong = ~(full < threshold)
     for w in range(n_win):
         hit = np.nonzero(strong[:, w])[0]
@@ -123,7 +124,6 @@ def middle_scan_windows(windows, adapter_seqs, scoring, threshold, device=0):
     """Drop-in for custom_porechop_abi_amd.engine.middle_scan computed by the oracle (CPU): the
     reference's loop (porechop_abi/nanopore_read.py:236-246) restated per read -- for each adapter
     in order, re-align while the full identity is not below the threshold, masking each hit."""
-    from custom_porechop_abi_amd.engine import pid6
     codes, offs, lens = windows
     out = []
     for w, (o, l) in enumerate(zip(offs.tolist(), lens.tolist())):
@@ -131,7 +131,7 @@ def middle_scan_windows(windows, adapter_seqs, scoring, threshold, device=0):
         for a, adp in enumerate(adapter_seqs):
             while True:
                 r = align(masked, adp, scoring)
-                full = 0.0 if r[0] == -1 else float(pid6(np.array([r[5]]), np.array([r[7]]))[0])
+                full = 0.0 if r[0] == -1 else float(ref_pid6(np.array([r[5]]), np.array([r[7]]))[0])
                 if full < threshold:
                     break
                 rs, rend = (r[0], r[1] + 1) if r[0] != -1 else (-1, 0)
@@ -199,14 +199,13 @@ def middle_scan_seqs_threaded(addr, lens, adapter_seqs, scoring, threshold, devi
 
 def best_full_identity_windows(windows, adapter_seqs, scoring, best=None, device=0, best_device_ptr=None):
     """Drop-in for custom_porechop_abi_amd.engine.best_full_identity computed by the oracle (CPU)."""
-    from custom_porechop_abi_amd.engine import pid6
     assert best_device_ptr is None, 'the CPU stand-in has no device buffer'
     n_win, n_adp = len(windows[2]), len(adapter_seqs)
     out = np.zeros(n_adp, np.float64) if best is None else np.array(best, dtype=np.float64)
     if n_win == 0 or n_adp == 0:
         return out
     res = align_windows(windows, adapter_seqs, scoring)
-    full = np.where(res[0] == -1, 0.0, pid6(res[5], res[7])).reshape(n_adp, n_win)
+    full = np.where(res[0] == -1, 0.0, ref_pid6(res[5], res[7])).reshape(n_adp, n_win)
     return np.maximum(out, full.max(axis=1))
 
 
@@ -216,7 +215,6 @@ def end_decisions_windows(codes, start_windows, end_windows, start_seqs, end_seq
     alignments of both sides, find_start_trim / find_end_trim's rules (nanopore_read.py:175-217)
     restated over them, the recorded alignments as (read, adapter, rs, re, m, l1, l2) lists in the
     reference's order, and the listed adapters' full identities."""
-    from custom_porechop_abi_amd.engine import pid6
     codes = np.asarray(codes, np.uint8)             # an engine.StrWindows is gathered here
     n = len(start_windows[1])
     trims, lists, fulls = [], [], []
@@ -230,8 +228,8 @@ def end_decisions_windows(codes, start_windows, end_windows, start_seqs, end_seq
         rs = res[0]
         failed = rs == -1
         re1 = np.where(failed, 0, res[1] + 1)
-        part = np.where(failed, 0.0, pid6(res[5].ravel(), res[6].ravel()).reshape(na, n))
-        full = np.where(failed, 0.0, pid6(res[5].ravel(), res[7].ravel()).reshape(na, n))
+        part = np.where(failed, 0.0, ref_pid6(res[5].ravel(), res[6].ravel()).reshape(na, n))
+        full = np.where(failed, 0.0, ref_pid6(res[5].ravel(), res[7].ravel()).reshape(na, n))
         edge = (re1 != end_size) if side == 0 else (rs != 0)
         ok = (part > end_threshold) & edge & (re1 - rs >= min_trim_size)
         amount = np.where(ok, (re1 + extra_trim) if side == 0 else (end_size - rs) + extra_trim, 0)

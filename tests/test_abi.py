@@ -9,6 +9,8 @@ import re
 import numpy as np
 import pytest
 
+from tests import identity_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -58,6 +60,13 @@ def test_pid6_host_exact():
     exp = np.array([float('%f' % (100.0 * a / b)) for a, b in zip(m.tolist(), l.tolist())])
     assert np.array_equal(got, exp)
     assert math.isnan(engine.pid6(np.array([0], np.int32), np.array([0], np.int32))[0])
+    # the lengths whose products land on k + 0.5 (tests/identity_ref.py): the correction that the
+    # exact product decides first runs at l = 64000, far past the grid above
+    assert min(identity_ref.corrected_ties(64000), identity_ref.corrected_ties(128000)) >= 10000
+    m, l = identity_ref.tie_grid()
+    got, exp = engine.pid6(m, l), identity_ref.ref_pid6(m, l)
+    bad = np.nonzero(got != exp)[0]
+    assert len(bad) == 0, [(int(m[i]), int(l[i]), got[i], exp[i]) for i in bad[:5]]
 
 
 def test_compute_fails_loudly_without_device():

@@ -11,7 +11,8 @@ import tempfile
 
 import pytest
 
-from tests import golden_lib, oracle_lib
+from tests import golden_lib, identity_ref, oracle_lib
+from tests.identity_ref import ref_pid6_scalar
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -142,6 +143,11 @@ def test_pid6_matches_text_round_trip(model):
     for l in range(1, 700):
         for m in range(0, l + 1):
             assert model.pcabi_model_pid6(m, l) == float('%f' % (100.0 * m / l))
+    # products that land on k + 0.5 (tests/identity_ref.py); the reference side alone shows that
+    # the block holds ties rint(p) gets wrong, so passing means the correction ran and was right
+    assert min(identity_ref.corrected_ties(64000), identity_ref.corrected_ties(128000)) >= 10000
+    for m, l in zip(*(a.tolist() for a in identity_ref.tie_grid())):
+        assert model.pcabi_model_pid6(m, l) == float('%f' % (100.0 * m / l)), (m, l)
 
 
 def test_packed_core_extra_padding_rows(model):
@@ -345,8 +351,6 @@ def test_score_filter_equals_best_score(model):
 def test_score_filter_threshold_is_a_lower_bound(model):
     """Every alignment whose full identity reaches the threshold scores at least the filter's
     bound (checked on hits of mutated adapters, where the bound is tight)."""
-    from custom_porechop_abi_amd.engine import pid6
-    import numpy as np
     rng = random.Random(29)
     checked = 0
     for k in range(3000):
@@ -370,7 +374,7 @@ def test_score_filter_threshold_is_a_lower_bound(model):
         res = oracle_lib.align(r, a, sc)
         if res[0] == -1:
             continue
-        full = float(pid6(np.array([res[5]]), np.array([res[7]]))[0])
+        full = ref_pid6_scalar(res[5], res[7])
         if full >= thr:
             assert res[4] >= model.pcabi_model_filter_threshold(L, thr, *sc), (sc, thr, r, a, res)
             checked += 1

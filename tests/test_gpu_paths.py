@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import path_oracle_lib
+from tests.identity_ref import ref_pid6
 from tests.test_gpu_parity import SCHEMES, _mutate, _rand_seq
 from tests.test_paths_cpu import DEFAULT, KNOWN
 
@@ -276,7 +277,7 @@ def test_adapter_profile(gpu_lib):
     pack = engine.SeqPack(reads)
     win = pack.views(np.zeros(len(reads), np.int64), pack.lengths)
     res = engine.align(win, adps, DEFAULT, pairs=pairs)
-    select = engine.pid6(res[5], res[7]) >= 75
+    select = ref_pid6(res[5], res[7]) >= 75
     assert 200 < select.sum() < len(select)
     exp = _profile_reference(reads, adps, pairs, select, DEFAULT)
     assert exp[:, :, 5].sum() > 0 and exp[:, :, 6].sum() > 0 and exp[:, :, :4].sum() > 5000
