@@ -52,14 +52,11 @@
 
 #include "../../include/pcabi.h"
 #include "pcabi_dp.h"
+// this unit's entry points (namespace pcabi_seed), the scratch owner and g_buf_gen: the scratch
+// generation the middle scan's captured round graphs are keyed on (a reallocation, a new plan or new
+// capacities here change addresses or launch arguments those graphs hold)
+#include "pcabi_host.h"
 
-namespace pcabi_internal {
-int fail(int code, const std::string &msg);
-}
-// pcabi_engine.hip: the scratch generation its captured round graphs are keyed on (a reallocation,
-// a new plan or new capacities here change addresses or launch arguments those graphs hold)
-extern std::atomic<uint64_t> g_buf_gen;
-void pcabi_poison(void *p, size_t bytes);   // pcabi_engine.hip: PCABI_POISON=1 fills fresh scratch
 using pcabi_internal::fail;
 
 #define SD_TRY(expr)                                                                                          \
@@ -1132,31 +1129,6 @@ __global__ __launch_bounds__(256) void k_bound_reset(int32_t *bound, int64_t n, 
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(bytes, 1 << 16);
-        g_buf_gen.fetch_add(1);
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(PCABI_E_NOMEM, "hipMalloc failed (seeds, " + std::to_string(want) + " bytes): " + hipGetErrorString(e));
-        }
-        cap = want;
-        pcabi_poison(p, want);
-        return 0;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct State {
     // the second band class runs beside the first on a side stream (fork / join by events)
     hipStream_t side = nullptr, side2 = nullptr;   // class 1's inside tasks; both classes' edge tasks
@@ -1179,7 +1151,7 @@ struct State {
     size_t lds_bytes = 0;                         // the whole probe image (k_seed_expand1)
     int32_t adp_bytes = 0;                        // flat adapter table, dword-rounded
     ScanArgs a{};
-    Buf tabs, adp, adp_off, adp_len, adp_meta, task, cnt, bound, thr, cands, ccnt, raw, rawcnt, segcum, scantmp;
+    Scratch<> tabs, adp, adp_off, adp_len, adp_meta, task, cnt, bound, thr, cands, ccnt, raw, rawcnt, segcum, scantmp;
     int pin_nc4[kCls] = {0, 0};                   // class c's pinned band slot (uint4 per lane), 0: band_best
     int32_t n_adp = 0;
     int64_t cap = 0, ecap = 0, ccap = 0, raw_cap = 0;
@@ -1187,7 +1159,7 @@ struct State {
     int n_slab = 0;                               // raw-hit slabs: one per scan wave
     int expand_blocks = 0;                        // resident k_seed_expand1 blocks
     int pin_blocks[kCls] = {0, 0};                // resident k_seed_band_pin blocks per class
-    Buf vseed;                                    // verified seeds (device rounds)
+    Scratch<> vseed;                                    // verified seeds (device rounds)
     std::vector<int32_t> ucert;                   // per adapter: the candidate windows' certificate bound
     int64_t vcap = 0;
     int shrink = 0;                               // tests: the next seeding runs with 1 raw-hit slab entry (1)
@@ -1195,7 +1167,7 @@ struct State {
     bool serial = false;                          // the next seeding's band launches all on the caller's stream
     hipEvent_t *pev = nullptr;                    // profile (profile_events): 4 marks recorded on the caller's stream
     bool bstats_on = false;                       // profile (profile_band_stats): the pinned bands count their work
-    Buf bstats;                                   //   into 2 classes x (lane-rows issued, active, tasks, passes)
+    Scratch<> bstats;                                   //   into 2 classes x (lane-rows issued, active, tasks, passes)
     VerOut ver{nullptr, nullptr, nullptr, 0};     // the band launches' record target (list nullptr: off)
 };
 
@@ -1556,9 +1528,7 @@ int enqueue_seeds(State *s, const uint8_t *codes, const int64_t *v_off, const in
     if (s->raw_cap == 0 || s->cap == 0) {
         // first sizing; PCABI_MIDDLE_INIT_CAPS="raw,task[,slots]" (tests: small buffers that overflow
         // and grow) overrides the defaults, 0 keeps one
-        int64_t raw = 0, task = 0;
-        if (const char *e = std::getenv("PCABI_MIDDLE_INIT_CAPS"))
-            if (std::sscanf(e, "%lld,%lld", (long long *)&raw, (long long *)&task) < 1) raw = task = 0;
+        const int64_t raw = pcabi_internal::middle_init_caps().raw, task = pcabi_internal::middle_init_caps().task;
         // (4096 raw hits per r03 scan block: the same total for the byte-map scan's wave slabs)
         if (s->raw_cap == 0) s->raw_cap = raw > 0 ? std::max<int64_t>(raw, s->n_slab) : (int64_t)std::max(grid * 4096, 1536 * 4096);
         if (s->cap == 0) s->cap = task > 0 ? task : 1 << 22;

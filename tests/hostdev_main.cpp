@@ -6,9 +6,11 @@
 #include <utility>
 
 #include "../custom_porechop_abi_amd/csrc/pcabi_hostdev.h"
+#include "../custom_porechop_abi_amd/csrc/pcabi_scratch.h"
 
 using pcabi_internal::holds;
 using pcabi_internal::Owned;
+using pcabi_internal::ScratchOf;
 
 namespace {
 
@@ -116,6 +118,36 @@ int main() {
         CHECK(!t.kept(1000, 51) && !t.kept(1001, 50));
     }
     CHECK(Fake::live == 0 && Fake::frees + 1 == Fake::allocs);   // the failed allocation has no free
+    {   // 6. the scratch owner's rule (pcabi_scratch.h): counts in elements; nothing when they fit, else
+        //    the old block goes first and max(count elements, 64 KiB) come -- one allocation per growth
+        //    (the real policy bumps the scratch generation once per allocation)
+        Fake::reset(4);
+        ScratchOf<Fake, int32_t> s;
+        CHECK(s.ensure(0) == 0 && s.p == nullptr && Fake::allocs == 0);
+        CHECK(s.ensure(10) == 0 && s.cap == 16384 && Fake::allocs == 1);             // 64 KiB of int32
+        int32_t *p = s;
+        p[16383] = 7;
+        CHECK(s.ensure(16384) == 0 && s.ensure(1) == 0 && s.p == p && Fake::allocs == 1 && Fake::frees == 0);
+        CHECK(s.ensure(16385) == 0 && s.cap == 16385 && Fake::allocs == 2 && Fake::frees == 1 && Fake::peak == 1);
+        s[16384] = 8;
+        CHECK(s.ensure(40000) == 0 && s.cap == 40000 && Fake::allocs == 3 && Fake::frees == 2 && Fake::peak == 1);
+        CHECK(s.ensure(50000) == kNoMemory && s.p == nullptr && s.cap == 0 && Fake::live == 0 && Fake::frees == 3);
+        CHECK(s.ensure(5) == 0 && s.p != nullptr && s.cap == 16384 && Fake::allocs == 5);   // the next call allocates
+        ScratchOf<Fake> b;                                                           // bytes by default
+        CHECK(b.ensure(1) == 0 && b.cap == 65536 && b.ensure(65537) == 0 && b.cap == 65537);
+        b[65536] = 1;
+        // PCABI_MIDDLE_INIT_CAPS: two to four fields, 0 (or a missing field) keeps the default
+        using pcabi_internal::parse_middle_init_caps;
+        auto caps = [](const char *e, int64_t raw, int64_t task, int64_t slots, int64_t arena) {
+            const pcabi_internal::MiddleInitCaps c = parse_middle_init_caps(e);
+            return c.raw == raw && c.task == task && c.slots == slots && c.arena == arena;
+        };
+        CHECK(caps(nullptr, 0, 0, 0, 0) && caps("", 0, 0, 0, 0) && caps("x", 0, 0, 0, 0));
+        CHECK(caps("256,0,0", 256, 0, 0, 0) && caps("0,64,0", 0, 64, 0, 0) && caps("0,0,128", 0, 0, 128, 0));
+        CHECK(caps("256,64,128", 256, 64, 128, 0) && caps("0,0,0,4096", 0, 0, 0, 4096) && caps("7,9", 7, 9, 0, 0));
+        CHECK(caps("-1,-2,-3,-4", 0, 0, 0, 0) && caps("5", 5, 0, 0, 0));
+    }
+    CHECK(Fake::live == 0);
     // the copy and the clock the stages share
     std::vector<uint8_t> src(33u << 20), dst(src.size());
     for (size_t i = 0; i < src.size(); i += 4093) src[i] = (uint8_t)(i * 31);

@@ -1,7 +1,7 @@
 """GPU parity of the middle scan's product paths that the default inputs rarely force, vs the
 oracle's masked loop (the reference's find_middle_adapters, porechop_abi/nanopore_read.py:219-252):
 
-  * overflow recovery of the queued device rounds (pcabi_engine.hip middle_device_rounds): a round
+  * overflow recovery of the queued device rounds (pcabi_middle.hip middle_device_rounds): a round
     whose raw-hit slabs (flag 1), band task regions (2) or candidate-DP task slots (4) overflow keeps
     nothing, is queued again and the scan still equals the oracle -- forced in round 1 by small
     initial buffers that must grow (PCABI_MIDDLE_INIT_CAPS, a fresh scan through the device ABI),
@@ -290,6 +290,34 @@ def test_overflow_in_a_round_is_dropped_and_requeued(gpu_lib, monkeypatch, reads
     n1, f1 = _requeues(gpu_lib)
     assert n1 - n0 >= len(fault.split(',')), 'the injected rounds did not overflow'
     assert np.array_equal(_sorted(got), exp)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('windows', ['0', '1'])
+@pytest.mark.parametrize('fault', ['', '17:4'])
+def test_rounds_wrap_past_the_slot_count(gpu_lib, monkeypatch, windows, fault):
+    """Reads with 40 planted copies each hit in more rounds than the device holds round slots (16):
+    one round yields at most one hit per read, so a read with 20+ hits takes the scan past the wrap,
+    where the last slot's reads move to slot 0 and the round numbers go on from there. With
+    PCABI_MIDDLE_FAULT=17:4 a round after the wrap overflows its candidate-DP task slots, keeps
+    nothing and is queued again. The hits equal the oracle's, with and without candidate windows."""
+    from custom_porechop_abi_amd import engine
+    reads = _reads(11, 6, 3000, 90.0, copies=(40,))
+    pack = engine.SeqPack(reads)
+    views = pack.views(np.zeros(len(reads), np.int64), pack.lengths)
+    exp = oracle_lib.middle_scan_threaded(views, ADPS, SC, 90.0)
+    assert np.bincount(exp[0]).max() >= 20, 'want a read that hits in more rounds than there are slots'
+    monkeypatch.setenv('PCABI_MIDDLE_SEEDS', '2')
+    monkeypatch.setenv('PCABI_MIDDLE_WINDOWS', windows)
+    if fault:
+        monkeypatch.setenv('PCABI_MIDDLE_FAULT', fault)
+    n0, _ = _requeues(gpu_lib)
+    got = _dev_scan(gpu_lib, views, ADPS, SC, 90.0)
+    n1, flags = _requeues(gpu_lib)
+    if fault:
+        assert n1 > n0, 'the injected round did not overflow'
+        assert flags & 4, flags
+    assert np.array_equal(_sorted(got), _sorted(exp))
 
 
 @pytest.mark.gpu

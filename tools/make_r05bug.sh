@@ -6,12 +6,12 @@
 set -e
 cd "$(dirname "$0")/.."
 src=custom_porechop_abi_amd/csrc
-sed -e 's/    HIP_TRY(hipMemsetAsync(d_slots, 0, 4 \* sizeof(int64_t), st));/    \/\/ (r05bug variant: the plans'"'"' needs left unwritten)/' \
-    -e 's/const int64_t most = std::max(need, windows ? need2 : (int64_t)0);/const int64_t most = std::max(need, need2);   \/\/ (r05bug variant)/' \
-    $src/pcabi_engine.hip > $src/_engine_r05bug.hip
-test "$(grep -c 'r05bug variant' $src/_engine_r05bug.hip)" = 2
+sed -e 's/    HIP_TRY(hipMemsetAsync(&c.ctl->slots, 0, offsetof(RoundCtl, bump) - offsetof(RoundCtl, slots), st));/    \/\/ (r05bug variant: the plans'"'"' needs left unwritten)/' \
+    -e 's/const int64_t most = std::max(h.need, c.windows ? h.need2 : (int64_t)0);/const int64_t most = std::max(h.need, h.need2);   \/\/ (r05bug variant)/' \
+    $src/pcabi_middle.hip > $src/_middle_r05bug.hip
+test "$(grep -c 'r05bug variant' $src/_middle_r05bug.hip)" = 2
 mkdir -p build/vobj perf_variants
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -o build/vobj/engine_r05bug.o $src/_engine_r05bug.hip
-rm -f $src/_engine_r05bug.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o perf_variants/r05bug.so build/vobj/engine_r05bug.o $(ls build/*.o | grep -v pcabi_engine.o) -lz
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -o build/vobj/middle_r05bug.o $src/_middle_r05bug.hip
+rm -f $src/_middle_r05bug.hip
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o perf_variants/r05bug.so build/vobj/middle_r05bug.o $(ls build/*.o | grep -v pcabi_middle.o) -lz
 echo built perf_variants/r05bug.so
