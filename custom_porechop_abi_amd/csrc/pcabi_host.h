@@ -1,7 +1,8 @@
 // pcabi_host.h -- the host-side declarations that cross between the engine (pcabi_engine.hip), the
-// middle scan (pcabi_middle.hip) and the middle-scan seeds (pcabi_seed.hip): the prepared adapter
-// table, the fork / join of independent launches, the bucket dispatch and its layout questions, the
-// tile layout, and the seeds' entry points. Host code only: the kernel units include pcabi_kern.h.
+// host-buffer entry points (pcabi_hostapi.hip), the middle scan (pcabi_middle.hip) and the middle-scan
+// seeds (pcabi_seed.hip): the prepared adapter table, the fork / join of independent launches, the
+// bucket layout, the bucket dispatch and its layout questions, the tile layout, and the seeds' entry
+// points. Host code only: the kernel units include pcabi_kern.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,9 +37,9 @@ struct pcabi_adapters {
     std::vector<uint8_t> hcodes;             // host copy of the adapters (middle-scan seeds)
     std::vector<int32_t> hoff, hlen;
     int32_t count[pcabi_eng::kNumBuckets] = {};
-    uint32_t *pad[pcabi_eng::kNumBuckets] = {};
-    int32_t *len[pcabi_eng::kNumBuckets] = {};
-    int32_t *id[pcabi_eng::kNumBuckets] = {};
+    // the buckets' device arrays (plain device memory: no scratch generation, no poison)
+    pcabi_internal::DevBuf<uint32_t> pad[pcabi_eng::kNumBuckets];
+    pcabi_internal::DevBuf<int32_t> len[pcabi_eng::kNumBuckets], id[pcabi_eng::kNumBuckets];
     // Other layouts of the same adapters, built on first use by adapters_for() for a scoring this
     // layout cannot serve (gap costs >= 0 under padded register buckets, a merge made for another
     // scoring) or for long windows that need the striped core; kept until the table is destroyed
@@ -79,6 +80,20 @@ bool chunkable(int b, bool packed);
 int dispatch(int b, const KParams &p, bool affine, hipStream_t st, int packed);
 bool bucket_packed_ok(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc);
 int bucket_pack_mode(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc);
+// cross shape, pack mode 2: the bucket's gap-extend frame into p.shift_p / p.shift_b (0: none)
+void bucket_shift(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc, int pack_mode, KParams &p);
+
+// Host-side layout of a bucket's adapter table, for a caller that uploads its own (pcabi_align_host).
+struct BucketHost {
+    std::vector<uint8_t> pad;   // n * RPL bytes (striped: n * rt)
+    std::vector<int32_t> len, id;
+    int rt = 0;                 // striped: table rows per adapter
+};
+void build_buckets(const uint8_t *adp_codes, const int32_t *adp_off, const int32_t *adp_len, int32_t n_adp,
+                   const pcabi::Scoring &sc, BucketHost (&bk)[kNumBuckets], bool merge = true, bool allow_wide = true,
+                   bool all_striped = false);
+int check_adapter_lens(const int32_t *adp_len, int32_t n_adp);           // every length in 1..MAX_STRIPED_LEN
+bool needs_striped(const pcabi::Scoring &sc, int max_L, int64_t max_win);   // long windows, unbounded path span
 
 }  // namespace pcabi_eng
 

@@ -1,5 +1,5 @@
-// pcabi_scratch.h -- the owner of the engine's, the middle scan's and the seeds' device scratch
-// (pcabi_engine.hip, pcabi_middle.hip, pcabi_seed.hip), built on Owned<Mem, T> (pcabi_hostdev.h), and
+// pcabi_scratch.h -- the owner of the host-buffer engines', the middle scan's and the seeds' device
+// scratch (pcabi_hostapi.hip, pcabi_middle.hip, pcabi_seed.hip), built on Owned<Mem, T> (pcabi_hostdev.h), and
 // the one reader of PCABI_MIDDLE_INIT_CAPS. What names a HIP type sits under __HIPCC__; the growth
 // rule compiles with a plain C++ compiler (tests/hostdev_main.cpp runs it over a fake allocator).
 #pragma once

@@ -217,6 +217,42 @@ def test_end_decisions_from_strings_on_gpu(gpu_lib):
 
 
 @pytest.mark.gpu
+def test_end_decisions_kept_buffers_shrink_and_grow_on_gpu(gpu_lib, monkeypatch):
+    """One device's kept buffers through calls of 257, 1 and 513 reads (across the 256-window tile
+    boundary, smaller then larger than what is held), one without start adapters, one whose list
+    capacity is too small (refused, then asked for again), and one window of 33,000 bases (the lists
+    come back uncompacted: window + adapter >= 32768); each == the CPU oracle."""
+    import random
+    import numpy as np
+    from custom_porechop_abi_amd import engine, porechop_abi as P
+    from custom_porechop_abi_amd.nanopore_read import NanoporeRead
+    seqs, ad = _edge_reads(n=513)
+    starts = [a.start_sequence[1] for a in ad if a.start_sequence]
+    ends = [a.end_sequence[1] for a in ad if a.end_sequence]
+    sc = [3, -6, -5, -2]
+
+    def run(sub, e, starts, strings):
+        reads = [NanoporeRead('r%d' % i, s, '') for i, s in enumerate(sub)]
+        lz, sw, ew = P.end_windows_pack(reads, e, lazy=True)
+        got = engine.end_decisions(lz if strings else np.asarray(lz), sw, ew, starts, ends, sc, e, 2, 75.0, 4)
+        ora = oracle_lib.end_decisions_windows(lz, sw, ew, starts, ends, sc, e, 2, 75.0, 4)
+        for g, x in zip(got[:4], ora[:4]):
+            assert np.array_equal(np.asarray(g, np.int64), np.asarray(x, np.int64))
+        return got
+
+    run(seqs[:257], 150, starts, True)
+    run(seqs[:1], 150, [], False)
+    # a capacity of 8 or 9 alignments per side: the first answer is the counts alone
+    monkeypatch.setattr(engine, '_END_LIST_RATIO', [-1016 / (513 * 1.25)])
+    got = run(seqs, 150, starts, True)
+    assert max(got[2].shape[1], got[3].shape[1]) > 9
+    rng = random.Random(11)
+    long_read = starts[0] + ''.join(rng.choice('ACGT') for _ in range(40000)) + ends[0]
+    got = run([long_read], 33000, starts, False)
+    assert got[2].shape[1] > 0 and got[3].shape[1] > 0
+
+
+@pytest.mark.gpu
 def test_middle_cut_ranges_on_device(gpu_lib):
     """pcabi_middle_cuts (the device epilogue of the middle scan) == NanoporeRead._apply_middle_hit's
     middle_trim_positions (nanopore_read.py:242-250) for random hits in discovery order: per read,
