@@ -157,6 +157,10 @@ def lib():
         'pcabi_fastx_keep_aux': ([c_p, c_int], c_int),
         'pcabi_reads_aux': ([c_p, c_p, c_p, c_p], c_int),
         'pcabi_fastx_bam_header': ([c_p, c_p, c_p], c_int),
+        'pcabi_mods_plan': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p], c_int),
+        'pcabi_mods_remap': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_mods_counts': ([c_int, c_p, c_p], None),
+        'pcabi_mods_last_times': ([c_int, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -199,7 +203,8 @@ def exported_symbols():
             'pcabi_bgzf_write_eof', 'pcabi_bam_index', 'pcabi_bam_unpack_dev', 'pcabi_bam_unpack_host',
             'pcabi_bam_last_times', 'pcabi_bgzf_scratch_bytes', 'pcabi_bgzf_dev', 'pcabi_bam_pack_plan',
             'pcabi_bam_pack_dev', 'pcabi_bam_pack_host', 'pcabi_bam_pack_last_times', 'pcabi_reads_write_bam',
-            'pcabi_fastx_keep_aux', 'pcabi_reads_aux', 'pcabi_fastx_bam_header']
+            'pcabi_fastx_keep_aux', 'pcabi_reads_aux', 'pcabi_fastx_bam_header', 'pcabi_mods_plan', 'pcabi_mods_remap',
+            'pcabi_mods_counts', 'pcabi_mods_last_times']
 
 
 class CrossRegion(ctypes.Structure):

@@ -151,8 +151,8 @@ struct Span {
 std::mutex g_prof_mu;
 bool g_prof = false;
 std::vector<Span *> g_spans;
-double g_ms[5] = {0, 0, 0, 0, 0};   // [4]: k_bam_pack
-int64_t g_unpack_bytes = 0, g_pack_bytes = 0;
+double g_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // [4]: k_bam_pack, [5]: k_mods_plan, [6]: k_mods_write
+int64_t g_unpack_bytes = 0, g_pack_bytes = 0, g_mods_bytes = 0;
 
 void harvest() {   // g_prof_mu held; the spans' streams are idle
     for (Span *s : g_spans) {
@@ -175,7 +175,8 @@ bool prof_on() {
     return g_prof;
 }
 
-// kind: 0 k_inflate, 1 k_bam_unpack, 2 copies to the device, 3 copies from the device, 4 k_bam_pack
+// kind: 0 k_inflate, 1 k_bam_unpack, 2 copies to the device, 3 copies from the device, 4 k_bam_pack,
+// 5 k_mods_plan, 6 k_mods_write
 void *prof_begin(void *stream, int kind) {
     Span *s = new Span();
     s->kind = kind;
@@ -314,6 +315,7 @@ struct PackDev {
     DevBuf<int64_t> d_len;
     PinBuf<> p_z;      // the compressed bytes, pinned
     Stream st;
+    ModsDev *mods = nullptr;   // the remap's device side (pcabi_mods.hip), made at its first use
 };
 // kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
 // HIP runtime that may already have shut down
@@ -321,14 +323,16 @@ PackDev &g_pack = *new PackDev;
 std::mutex g_pack_mu;
 }  // namespace
 
-int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
-                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
-                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink) {
+namespace {
+int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, BamWriteJob job,
+                  const ModsTables *mods, const std::function<void(BamWriteJob *)> *layout,
+                  const std::function<void(const uint8_t *, int64_t)> &sink) {
     std::lock_guard<std::mutex> lk(g_pack_mu);
     if (device < 0) PCABI_TRY(hipGetDevice(&device));
     if (g_pack.device >= 0 && g_pack.device != device) {
         (void)hipSetDevice(g_pack.device);
         g_pack.st.release();
+        mods_dev_free(g_pack.mods);
         g_pack = PackDev();
     }
     PCABI_TRY(hipSetDevice(device));
@@ -337,24 +341,39 @@ int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uin
         if (int rc = g_pack.st.create()) return rc;
     if (int rc = g_pack.d_len.reserve(8, 8)) return rc;
     hipStream_t st = g_pack.st;
+    // the letters first: the remap counts them where the pack reads them
+    if (int rc = g_pack.buf[0].reserve(seq_n + 64, std::max<int64_t>(seq_n + 64 + seq_n / 4, 1 << 20))) return rc;
+    if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(g_pack.buf[0], seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
+    if (mods) {
+        if (!g_pack.mods) g_pack.mods = mods_dev_new();
+        if (int rc = mods_plan_any(device, g_pack.mods, nullptr, st, seq, g_pack.buf[0], seq_n, mods->tags, mods->tags_n, mods->reads,
+                                   mods->n_reads, mods->parts, mods->n_parts, mods->usable))
+            return rc;
+        (*layout)(&job);
+    }
+    const uint8_t *head = job.head, *side = job.side;
+    const pcabi_bam_part *parts = job.parts;
+    const int64_t head_n = job.head_n, side_n = job.side_n, n_parts = job.n_parts, n_tiles = job.n_tiles, stream_n = job.stream_n;
+    if (stream_n <= 0) return 0;
     const int64_t block = PCABI_BGZF_BLOCK_CAP;
     const int64_t z_cap = pcabi_bgzf_bound(stream_n, std::max<int64_t>((stream_n + block - 1) / block, 1), 0);
     const int64_t sc = pcabi_bgzf_scratch_bytes(stream_n, block);
     if (z_cap < 0 || sc < 0) return z_cap < 0 ? z_cap : sc;
     const int64_t need[6] = {seq_n + 64, qual_n + 64, side_n + 64, n_parts * (int64_t)sizeof(pcabi_bam_part) + 64,
                              stream_n + 64, z_cap + 64};
-    for (int k = 0; k < 6; ++k)
+    for (int k = 1; k < 6; ++k)
         if (int rc = g_pack.buf[k].reserve(need[k], std::max<int64_t>(need[k] + need[k] / 4, 1 << 20))) return rc;
     if (int rc = g_pack.scratch.reserve(sc, sc + sc / 4)) return rc;
     uint8_t *d_seq = g_pack.buf[0], *d_qual = g_pack.buf[1], *d_side = g_pack.buf[2], *d_stream = g_pack.buf[4],
             *d_z = g_pack.buf[5];
     pcabi_bam_part *d_parts = (pcabi_bam_part *)g_pack.buf[3].p;
-    if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
     if (qual_n > 0) PCABI_TRY(hipMemcpyAsync(d_qual, qual, (size_t)qual_n, hipMemcpyHostToDevice, st));
     if (side_n > 0) PCABI_TRY(hipMemcpyAsync(d_side, side, (size_t)side_n, hipMemcpyHostToDevice, st));
     if (n_parts > 0)
         PCABI_TRY(hipMemcpyAsync(d_parts, parts, (size_t)n_parts * sizeof(pcabi_bam_part), hipMemcpyHostToDevice, st));
     if (head_n > 0) PCABI_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
+    if (mods)
+        if (int rc = mods_dev_write(g_pack.mods, st, mods->parts, mods->n_parts, d_side, side_n)) return rc;
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 4) : nullptr;
     if (int rc = launch_pack(st, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, n_tiles, d_stream, stream_n))
@@ -376,6 +395,27 @@ int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uin
     PCABI_TRY(hipStreamSynchronize(st));
     sink(g_pack.p_z, zn);
     return zn;
+}
+}  // namespace
+
+int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
+                      int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
+                      int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink) {
+    BamWriteJob job;
+    job.head = head, job.head_n = head_n, job.side = side, job.side_n = side_n;
+    job.parts = parts, job.n_parts = n_parts, job.n_tiles = n_tiles, job.stream_n = stream_n;
+    return write_dev(device, seq, seq_n, qual, qual_n, job, nullptr, nullptr, sink);
+}
+
+int64_t bam_write_mods_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables &mods,
+                           const std::function<void(BamWriteJob *)> &layout,
+                           const std::function<void(const uint8_t *, int64_t)> &sink) {
+    return write_dev(device, seq, seq_n, qual, qual_n, BamWriteJob(), &mods, &layout, sink);
+}
+
+void prof_add_bytes(int kind, int64_t bytes) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (kind == 5 || kind == 6) g_mods_bytes += bytes;
 }
 
 }  // namespace pcabi_internal
@@ -572,6 +612,19 @@ void pcabi_bam_pack_last_times(int reset, double *ms, int64_t *bytes) {
     if (reset) {
         g_ms[4] = 0;
         g_pack_bytes = 0;
+    }
+}
+
+void pcabi_mods_last_times(int reset, double *ms, int64_t *bytes) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    harvest();
+    int64_t dev_ns = 0;
+    const int64_t host_ns = mods_host_ns(reset, &dev_ns);
+    if (ms) ms[0] = g_ms[5], ms[1] = g_ms[6], ms[2] = 1e-6 * (double)host_ns, ms[3] = 1e-6 * (double)dev_ns;
+    if (bytes) *bytes = g_mods_bytes;
+    if (reset) {
+        g_ms[5] = g_ms[6] = 0;
+        g_mods_bytes = 0;
     }
 }
 

@@ -1,5 +1,5 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
 // the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
 // pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
 // compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
@@ -179,5 +179,52 @@ int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const p
 int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uint8_t *seq, int64_t seq_n, const uint8_t *qual,
                       int64_t qual_n, const uint8_t *side, int64_t side_n, const pcabi_bam_part *parts, int64_t n_parts,
                       int64_t n_tiles, int64_t stream_n, const std::function<void(const uint8_t *, int64_t)> &sink);
+// The same with modification tags to remap (pcabi_mods.hip): the letters go up once, the device sizes
+// the parts' tags (mods->parts[].len, mods->usable), `layout` then builds the side blob with a gap
+// behind each part's kept tags, sets mods->parts[].out to the gaps and fills the job; the gaps are
+// filled in the device copy of the blob before k_bam_pack runs.
+struct BamWriteJob {
+    const uint8_t *head = nullptr, *side = nullptr;
+    const pcabi_bam_part *parts = nullptr;
+    int64_t head_n = 0, side_n = 0, n_parts = 0, n_tiles = 0, stream_n = 0;
+};
+struct ModsTables {
+    const uint8_t *tags = nullptr;
+    int64_t tags_n = 0;
+    const pcabi_mods_read *reads = nullptr;
+    int64_t n_reads = 0;
+    pcabi_mods_part *parts = nullptr;
+    int64_t n_parts = 0;
+    uint8_t *usable = nullptr;
+};
+int64_t bam_write_mods_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables &mods,
+                           const std::function<void(BamWriteJob *)> &layout,
+                           const std::function<void(const uint8_t *, int64_t)> &sink);
+void prof_add_bytes(int kind, int64_t bytes);   // 5 k_mods_plan, 6 k_mods_write
+
+// ---- pcabi_io.cpp --------------------------------------------------------------------------------
+int io_thread_count();
+
+// ---- pcabi_mods.hip ------------------------------------------------------------------------------
+// the device half of the remap: the tag blob, the tables and the scratch tables of the plan before
+struct ModsDev;
+// the host build's tables, kept from its sizing pass (device < 0) for its writing pass
+struct ModsHost;
+// device < 0: the host build; else dev / stream / d_seq name the device side. Checks the tables
+// (PCABI_E_ARG), fills parts[].len and usable[], counts the reads.
+int mods_plan_any(int device, ModsDev *dev, ModsHost *keep, void *stream, const uint8_t *seq, const uint8_t *d_seq, int64_t seq_n,
+                  const uint8_t *tags, int64_t tags_n, const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts,
+                  int64_t n_parts, uint8_t *usable);
+int mods_dev_plan(ModsDev *d, void *stream, const uint8_t *d_seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
+                  const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts, int64_t n_parts, uint8_t *usable);
+int mods_dev_write(ModsDev *d, void *stream, const pcabi_mods_part *parts, int64_t n_parts, uint8_t *d_out, int64_t out_cap);
+void mods_write_host(ModsHost *keep, const uint8_t *seq, const uint8_t *tags, const pcabi_mods_read *reads, int64_t n_reads,
+                     const pcabi_mods_part *parts, int64_t n_parts, uint8_t *out);
+ModsHost *mods_host_new();
+void mods_host_free(ModsHost *h);
+ModsDev *mods_dev_new();
+// wall time the host build took, and the device plan step (copies up, kernel, lengths back): pcabi_mods_last_times
+int64_t mods_host_ns(int reset, int64_t *dev_plan_ns);
+void mods_dev_free(ModsDev *d);   // its device current
 
 }  // namespace pcabi_internal

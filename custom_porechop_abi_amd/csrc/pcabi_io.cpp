@@ -573,6 +573,8 @@ void fill_fastq(pcabi_reads *b, const char *T, const std::vector<Span> &rec, boo
 
 }  // namespace
 
+int pcabi_internal::io_thread_count() { return io_threads(); }
+
 extern "C" {
 
 static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **out) {
@@ -1728,6 +1730,62 @@ bool bgzf_member(const uint8_t *data, size_t n, std::vector<uint8_t> &z) {
     return true;
 }
 
+// The modification tags of one read's aux chain (include/pcabi.h pcabi_mods_read): -1 when it carries
+// none of MM ML MN Mm Ml; else its entry appended to *reads, the MM text and the ML values named where
+// they lie in the batch's aux bytes (the chain is aux[a0, a1)). What only the chain can tell -- not exactly one MM tag, a tag of the wrong type, a tag twice --
+// marks the read PCABI_MODS_BAD.
+int64_t mods_read_of(const uint8_t *aux, int64_t a0, int64_t a1, int64_t seq_off, int64_t l_seq, std::vector<pcabi_mods_read> *reads,
+                     int64_t part0) {
+    using namespace pcabi_bam;
+    const uint8_t *ax = aux + a0;
+    const int64_t an = a1 - a0;
+    pcabi_mods_read r;
+    std::memset(&r, 0, sizeof r);
+    r.seq_off = seq_off, r.part0 = part0, r.l_seq = (int32_t)l_seq;
+    r.mm_len = r.ml_len = r.mn = -1;
+    int n_mm = 0, n_ml = 0, n_mn = 0;
+    bool any = false;
+    for (int64_t at = 0; at < an;) {
+        const int64_t nx = aux_next(ax, an, at);
+        if (nx < 0) break;
+        const uint8_t *tg = ax + at;
+        if (tg[0] == 'M' && (tg[1] == 'M' || tg[1] == 'm')) {
+            any = true;
+            if (++n_mm > 1 || tg[2] != 'Z') r.flags |= PCABI_MODS_BAD;
+            else {
+                r.mm_off = a0 + at + 3, r.mm_len = (int32_t)(nx - at - 4);
+                if (tg[1] == 'm') r.flags |= PCABI_MODS_OLD_MM;
+            }
+        } else if (tg[0] == 'M' && (tg[1] == 'L' || tg[1] == 'l')) {
+            any = true;
+            if (++n_ml > 1 || tg[2] != 'B' || tg[3] != 'C') r.flags |= PCABI_MODS_BAD;
+            else {
+                r.ml_off = a0 + at + 8, r.ml_len = (int32_t)(nx - at - 8);
+                if (tg[1] == 'l') r.flags |= PCABI_MODS_OLD_ML;
+            }
+        } else if (tg[0] == 'M' && tg[1] == 'N') {
+            any = true;
+            int64_t v = -1;
+            switch (tg[2]) {
+                case 'c': v = (int8_t)tg[3]; break;
+                case 'C': v = tg[3]; break;
+                case 's': v = (int16_t)le16(tg + 3); break;
+                case 'S': v = le16(tg + 3); break;
+                case 'i': v = le32(tg + 3); break;
+                case 'I': v = (uint32_t)le32(tg + 3); break;
+                default: break;
+            }
+            if (++n_mn > 1 || v < 0 || v > INT32_MAX) r.flags |= PCABI_MODS_BAD;
+            else r.mn = (int32_t)v;
+        }
+        at = nx;
+    }
+    if (!any) return -1;
+    if (n_mm != 1) r.flags |= PCABI_MODS_BAD;
+    reads->push_back(r);
+    return (int64_t)reads->size() - 1;
+}
+
 }  // namespace
 
 extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
@@ -1742,76 +1800,136 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     const double t_begin = now_s();
     const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
     const bool have_aux = keep_aux && !b->aux_off.empty();
+    const bool remap = have_aux && keep_aux == 2;
     const bool no_qual = b->type == PCABI_FASTA;
-    // the parts and their side blob (name, then aux bytes), per thread's range of reads, then joined
     const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
-    std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
-    std::vector<std::vector<uint8_t>> t_side((size_t)nt);
-    std::vector<int64_t> t_emit((size_t)nt, 0);
-    fan_out(nt, [&](int t) {
-        std::vector<std::pair<int64_t, int64_t>> rg;
-        std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
-        std::vector<uint8_t> &side = t_side[(size_t)t];
-        for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
-            const int64_t ns_all = b->seq_off[i + 1] - b->seq_off[i];
-            t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
-                pcabi_bam_part p;
-                std::memset(&p, 0, sizeof p);
-                p.seq_src = b->seq_off[i] + s0;
-                p.qual_src = (no_qual || nq < ns) ? -1 : b->qual_off[i] + q0;
-                p.side_off = (int64_t)side.size();
-                p.l_seq = (int32_t)ns;
-                // the name: the header up to its first space or tab, at most 254 bytes, "*" when empty
-                size_t k = 0;
-                while (k < nn && k < (size_t)kMaxName && name[k] != ' ' && name[k] != '\t') ++k;
-                if (k == 0) side.push_back('*'), k = 1;
-                else side.insert(side.end(), name, name + k);
-                p.name_len = (int32_t)k;
-                if (have_aux) {
-                    const uint8_t *ax = b->aux.data() + b->aux_off[i];
-                    const int64_t an = b->aux_off[i + 1] - b->aux_off[i];
-                    if (!own && s0 == 0 && ns == ns_all && b->as_stored[i]) {
-                        side.insert(side.end(), ax, ax + an);   // the whole read, as stored: verbatim
-                    } else {   // a changed read: without the tags that count its bases
-                        for (int64_t at = 0; at < an;) {
-                            const int64_t nx = aux_next(ax, an, at);
-                            if (nx < 0) break;
-                            if (!aux_positional(ax + at)) side.insert(side.end(), ax + at, ax + nx);
-                            at = nx;
-                        }
-                    }
-                    p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
-                }
-                parts.push_back(p);
-            }) ? 1 : 0;
+    // A part keeps its read's aux bytes verbatim when it is the whole read with the bases as stored.
+    auto verbatim = [&](int64_t i, bool own, int64_t s0, int64_t ns) {
+        return !own && s0 == 0 && ns == b->seq_off[i + 1] - b->seq_off[i] && b->as_stored[i];
+    };
+    // remap, first pass: the changed reads that carry modification tags and their parts (include/pcabi.h
+    // pcabi_mods_*; the tag blob is the batch's aux bytes), per thread's range of reads, then joined
+    std::vector<pcabi_mods_read> mreads;
+    std::vector<pcabi_mods_part> mparts;
+    std::vector<int64_t> mpart0((size_t)nt + 1, 0);   // a thread's first entry of mparts
+    std::vector<uint8_t> has_mods(remap ? (size_t)b->n : 0, 0);
+    if (remap) {
+        std::vector<std::vector<pcabi_mods_read>> t_reads((size_t)nt);
+        std::vector<std::vector<pcabi_mods_part>> t_parts((size_t)nt);
+        fan_out(nt, [&](int t) {
+            std::vector<std::pair<int64_t, int64_t>> rg;
+            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
+                int64_t mread = -2;   // the read's entry; -1: it carries none of the tags; -2: not looked yet
+                read_parts(wa, i, rg, [&](const char *, size_t, bool own, int64_t s0, int64_t ns, int64_t, int64_t) {
+                    if (verbatim(i, own, s0, ns)) return;
+                    if (mread == -2)
+                        mread = mods_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i],
+                                             b->seq_off[i + 1] - b->seq_off[i], &t_reads[(size_t)t], (int64_t)t_parts[(size_t)t].size());
+                    if (mread < 0) return;
+                    has_mods[(size_t)i] = 1;
+                    ++t_reads[(size_t)t][(size_t)mread].n_parts;
+                    t_parts[(size_t)t].push_back(pcabi_mods_part{0, (int32_t)mread, (int32_t)s0, (int32_t)ns, 0});
+                });
+            }
+        });
+        for (int t = 0; t < nt; ++t) {
+            const int64_t read_base = (int64_t)mreads.size(), part_base = (int64_t)mparts.size();
+            mpart0[(size_t)t] = part_base;
+            for (pcabi_mods_read r : t_reads[(size_t)t]) {
+                r.part0 += part_base;
+                mreads.push_back(r);
+            }
+            for (pcabi_mods_part p : t_parts[(size_t)t]) {
+                p.read += (int32_t)read_base;
+                mparts.push_back(p);
+            }
         }
-    });
+        mpart0[(size_t)nt] = (int64_t)mparts.size();
+    }
+    const bool mods = !mreads.empty();
+    std::vector<uint8_t> usable(mreads.size());
+    pcabi_internal::ModsTables mt;
+    mt.tags = b->aux.data(), mt.tags_n = (int64_t)b->aux.size(), mt.reads = mreads.data(), mt.n_reads = (int64_t)mreads.size();
+    mt.parts = mparts.data(), mt.n_parts = (int64_t)mparts.size(), mt.usable = usable.data();
     std::vector<pcabi_bam_part> parts;
-    std::vector<uint8_t> side;
-    int64_t emitted = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int64_t base = (int64_t)side.size();
-        for (pcabi_bam_part p : t_parts[(size_t)t]) {
-            p.side_off += base;
-            parts.push_back(p);
-        }
-        side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
-        emitted += t_emit[(size_t)t];
-    }
-    std::vector<uint8_t> head;
-    if (!append) {
-        static const char kDefault[] = "@HD\tVN:1.6\tSO:unknown\n";
-        const char *text = header_text ? header_text : kDefault;
-        const int64_t tn = header_text ? header_len : (int64_t)sizeof kDefault - 1;
-        const uint8_t magic[8] = {'B', 'A', 'M', 1, (uint8_t)tn, (uint8_t)(tn >> 8), (uint8_t)(tn >> 16), (uint8_t)(tn >> 24)};
-        head.insert(head.end(), magic, magic + 8);
-        head.insert(head.end(), text, text + tn);
-        head.insert(head.end(), 4, 0);   // n_ref = 0
-    }
+    std::vector<uint8_t> side, head;
+    int64_t emitted = 0, stream_n = 0;
     PackLayout lay;
-    lay.out = (int64_t)head.size();
-    for (pcabi_bam_part &p : parts) lay.place(&p);
-    const int64_t stream_n = lay.out;
+    // The parts and their side blob (name, then aux bytes), per thread's range of reads, then joined, and the
+    // chain planned. With sized modification tags (mparts[].len) a gap of the tags' length follows a part's
+    // kept tags, and mparts[].out names it.
+    auto layout = [&] {
+        std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
+        std::vector<std::vector<uint8_t>> t_side((size_t)nt);
+        std::vector<int64_t> t_emit((size_t)nt, 0);
+        fan_out(nt, [&](int t) {
+            std::vector<std::pair<int64_t, int64_t>> rg;
+            std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
+            std::vector<uint8_t> &side = t_side[(size_t)t];
+            int64_t mp = mpart0[(size_t)t];
+            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
+                t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+                    pcabi_bam_part p;
+                    std::memset(&p, 0, sizeof p);
+                    p.seq_src = b->seq_off[i] + s0;
+                    p.qual_src = (no_qual || nq < ns) ? -1 : b->qual_off[i] + q0;
+                    p.side_off = (int64_t)side.size();
+                    p.l_seq = (int32_t)ns;
+                    // the name: the header up to its first space or tab, at most 254 bytes, "*" when empty
+                    size_t k = 0;
+                    while (k < nn && k < (size_t)kMaxName && name[k] != ' ' && name[k] != '\t') ++k;
+                    if (k == 0) side.push_back('*'), k = 1;
+                    else side.insert(side.end(), name, name + k);
+                    p.name_len = (int32_t)k;
+                    if (have_aux) {
+                        const uint8_t *ax = b->aux.data() + b->aux_off[i];
+                        const int64_t an = b->aux_off[i + 1] - b->aux_off[i];
+                        if (verbatim(i, own, s0, ns)) {
+                            side.insert(side.end(), ax, ax + an);   // the whole read, as stored
+                        } else {   // a changed read: without the tags that count its bases
+                            for (int64_t at = 0; at < an;) {
+                                const int64_t nx = aux_next(ax, an, at);
+                                if (nx < 0) break;
+                                if (!aux_positional(ax + at)) side.insert(side.end(), ax + at, ax + nx);
+                                at = nx;
+                            }
+                            if (remap && has_mods[(size_t)i]) {   // its remapped tags go behind them
+                                mparts[(size_t)mp].out = (int64_t)side.size();
+                                side.resize(side.size() + (size_t)mparts[(size_t)mp].len);
+                                ++mp;
+                            }
+                        }
+                        p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
+                    }
+                    parts.push_back(p);
+                }) ? 1 : 0;
+            }
+        });
+        for (int t = 0; t < nt; ++t) {
+            const int64_t base = (int64_t)side.size();
+            for (pcabi_bam_part p : t_parts[(size_t)t]) {
+                p.side_off += base;
+                parts.push_back(p);
+            }
+            for (int64_t m = mpart0[(size_t)t]; m < mpart0[(size_t)t + 1]; ++m) mparts[(size_t)m].out += base;
+            side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
+            t_side[(size_t)t] = std::vector<uint8_t>();
+            emitted += t_emit[(size_t)t];
+        }
+        if (!append) {
+            static const char kDefault[] = "@HD\tVN:1.6\tSO:unknown\n";
+            const char *text = header_text ? header_text : kDefault;
+            const int64_t tn = header_text ? header_len : (int64_t)sizeof kDefault - 1;
+            const uint8_t magic[8] = {'B', 'A', 'M', 1, (uint8_t)tn, (uint8_t)(tn >> 8), (uint8_t)(tn >> 16), (uint8_t)(tn >> 24)};
+            head.insert(head.end(), magic, magic + 8);
+            head.insert(head.end(), text, text + tn);
+            head.insert(head.end(), 4, 0);   // n_ref = 0
+        }
+        lay.out = (int64_t)head.size();
+        for (pcabi_bam_part &p : parts) lay.place(&p);
+        stream_n = lay.out;
+    };
+    if (!mods) layout();   // nothing to size first
     const int64_t seq_n = (int64_t)b->seq.size(), qual_n = (int64_t)b->qual.size();
     // the file: opened before anything is compressed, written in large write() calls
     const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
@@ -1825,18 +1943,46 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     if (device >= 0) {
         g_write_times[0] = now_s() - t_begin;
         const double t0 = now_s();
-        if (stream_n > 0) {
-            const int64_t zn = pcabi_internal::bam_write_dev(device, head.data(), (int64_t)head.size(), (const uint8_t *)b->seq.data(),
-                                                             seq_n, (const uint8_t *)b->qual.data(), qual_n, side.data(),
-                                                             (int64_t)side.size(), parts.data(), (int64_t)parts.size(), lay.tiles,
-                                                             stream_n, write_timed);
-            if (zn < 0) {
-                ::close(fd);
-                return (int)zn;
-            }
+        double layout_s = 0;   // the side blob and the chain, built inside the device call once the tags are sized
+        int64_t zn = 0;
+        if (mods) {
+            zn = pcabi_internal::bam_write_mods_dev(device, (const uint8_t *)b->seq.data(), seq_n, (const uint8_t *)b->qual.data(), qual_n, mt,
+                                                    [&](pcabi_internal::BamWriteJob *job) {
+                                                        const double t1 = now_s();
+                                                        layout();
+                                                        layout_s = now_s() - t1;
+                                                        job->head = head.data(), job->head_n = (int64_t)head.size();
+                                                        job->side = side.data(), job->side_n = (int64_t)side.size();
+                                                        job->parts = parts.data(), job->n_parts = (int64_t)parts.size();
+                                                        job->n_tiles = lay.tiles, job->stream_n = stream_n;
+                                                    },
+                                                    write_timed);
+        } else if (stream_n > 0) {
+            zn = pcabi_internal::bam_write_dev(device, head.data(), (int64_t)head.size(), (const uint8_t *)b->seq.data(), seq_n,
+                                               (const uint8_t *)b->qual.data(), qual_n, side.data(), (int64_t)side.size(),
+                                               parts.data(), (int64_t)parts.size(), lay.tiles, stream_n, write_timed);
         }
-        g_write_times[1] = now_s() - t0 - g_write_times[2];
+        if (zn < 0) {
+            ::close(fd);
+            return (int)zn;
+        }
+        g_write_times[0] += layout_s;   // layout stays the host's share, the device's is what is left
+        g_write_times[1] = now_s() - t0 - g_write_times[2] - layout_s;
     } else {
+        pcabi_internal::ModsHost *keep = mods ? pcabi_internal::mods_host_new() : nullptr;
+        if (mods) {
+            const int rc = pcabi_internal::mods_plan_any(-1, nullptr, keep, nullptr, (const uint8_t *)b->seq.data(), nullptr, seq_n, mt.tags,
+                                                         mt.tags_n, mt.reads, mt.n_reads, mt.parts, mt.n_parts, mt.usable);
+            if (rc) {
+                pcabi_internal::mods_host_free(keep);
+                ::close(fd);
+                return rc;
+            }
+            layout();
+            pcabi_internal::mods_write_host(keep, (const uint8_t *)b->seq.data(), mt.tags, mt.reads, mt.n_reads, mt.parts, mt.n_parts,
+                                            side.data());
+            pcabi_internal::mods_host_free(keep);
+        }
         std::vector<uint8_t, NoInit<uint8_t>> stream;
         stream.resize((size_t)stream_n);
         if (!head.empty()) std::memcpy(stream.data(), head.data(), head.size());

@@ -828,3 +828,58 @@ def bam_pack(seq, qual, side, parts, out, device=0):
                                    arrs[2].size, _ptr(parts), parts.size, _ptr(out), out.size)
     check(int(rc), 'pcabi_bam_pack_host')
     return out
+
+
+# ---- modification tags remapped onto parts (csrc/pcabi_mods.h, csrc/pcabi_mods.hip) ---------------
+# include/pcabi.h pcabi_mods_read, pcabi_mods_part
+MODS_READ = np.dtype([('seq_off', np.int64), ('mm_off', np.int64), ('ml_off', np.int64), ('part0', np.int64),
+                      ('l_seq', np.int32), ('mm_len', np.int32), ('ml_len', np.int32), ('mn', np.int32),
+                      ('n_parts', np.int32), ('flags', np.int32)])
+MODS_PART = np.dtype([('out', np.int64), ('read', np.int32), ('s0', np.int32), ('ns', np.int32), ('len', np.int32)])
+MODS_OLD_MM, MODS_BAD, MODS_OLD_ML = 1, 2, 4
+
+
+def _mods_args(seq, tags, reads, name):
+    arrs = [np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, np.uint8)
+            for a in (seq, tags)]
+    if reads.dtype != MODS_READ or not reads.flags['C_CONTIGUOUS']:
+        raise ValueError('%s: reads is a C-contiguous MODS_READ array' % name)
+    return arrs
+
+
+def mods_plan(seq, tags, reads, parts, device=0):
+    """The lengths of every part's remapped MM / ML / MN tag bytes and which reads' tags are usable
+    (pcabi_mods_plan): on GPU `device`, or with the host build of the same code when device < 0.
+    seq: the reads' letters in the reader's orientation; tags: the MM texts and ML values the MODS_READ
+    array `reads` indexes; parts: a C-contiguous MODS_PART array with read / s0 / ns set, whose 'len' is
+    filled in place. Returns (parts, usable uint8 [n_reads])."""
+    seq, tags = _mods_args(seq, tags, reads, 'mods_plan')
+    if parts.dtype != MODS_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('mods_plan: parts is a C-contiguous MODS_PART array')
+    usable = np.zeros(reads.size, np.uint8)
+    rc = lib().pcabi_mods_plan(int(device), _ptr(seq), seq.size, _ptr(tags), tags.size, _ptr(reads), reads.size, _ptr(parts),
+                               parts.size, _ptr(usable))
+    check(int(rc), 'pcabi_mods_plan')
+    return parts, usable
+
+
+def mods_remap(seq, tags, reads, parts, out, device=0):
+    """Every part's tag bytes written to out[part.out, part.out + part.len) (pcabi_mods_remap): parts
+    as mods_plan left them, with 'out' set; out: a C-contiguous uint8 array, filled in place (bytes no
+    part owns keep their values) and returned."""
+    seq, tags = _mods_args(seq, tags, reads, 'mods_remap')
+    parts = np.ascontiguousarray(parts, MODS_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('mods_remap: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_mods_remap(int(device), _ptr(seq), seq.size, _ptr(tags), tags.size, _ptr(reads), reads.size, _ptr(parts),
+                                parts.size, _ptr(out), out.size)
+    check(int(rc), 'pcabi_mods_remap')
+    return out
+
+
+def mods_counts(reset=False):
+    """(reads whose modification tags were remapped, reads whose tags were dropped as not usable) since
+    the last reset (pcabi_mods_counts)."""
+    v = np.zeros(2, np.int64)
+    lib().pcabi_mods_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
+    return int(v[0]), int(v[1])

@@ -527,7 +527,7 @@ def get_albacore_barcode_from_path(albacore_path):
 
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
-                cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False):
+                cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False, keep_mods=False):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
     gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
@@ -543,7 +543,10 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     T, a FASTA batch has absent qualities, a quality-less FASTQ record's '+' padding is Phred 10.
     keep_aux: write the aux tags a batch read with keep_aux holds -- verbatim for a read written whole
     and as stored, without the position-dependent tags MM ML MN Mm Ml mv (dropped, not recomputed) for
-    a trimmed read, a split piece or a read from a reverse-strand record.
+    a trimmed read, a split piece or a read from a reverse-strand record. keep_mods (with keep_aux):
+    MM ML MN Mm Ml are recomputed for such a read instead (include/pcabi.h "base-modification tags"),
+    on gzip_device when it is given; a read whose tags are not usable loses them as before, and mv is
+    dropped either way. engine.mods_counts() tells how many reads went which way.
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -572,11 +575,13 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
     if bgzf and not (gz and gzip_device is not None):
         raise ValueError("bgzf applies to a '.gz' format compressed on a device (gzip_device)")
+    if keep_mods and not (keep_aux and out_format == 'bam'):
+        raise ValueError("keep_mods applies to out_format 'bam' with keep_aux")
     if out_format == 'bam':
         hdr = None if bam_header is None else bytes(bam_header)
         rc = L.pcabi_reads_write_bam(batch._h, os.fsencode(path), int(append), p(st), p(et), p(co), p(cu),
                                      int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel), hdr,
-                                     0 if hdr is None else len(hdr), int(bool(keep_aux)),
+                                     0 if hdr is None else len(hdr), 2 if keep_mods else int(bool(keep_aux)),
                                      -1 if gzip_device is None else int(gzip_device))
         if rc < 0:
             check(rc, 'pcabi_reads_write_bam')

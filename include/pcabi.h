@@ -912,7 +912,8 @@ void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
  *       same bytes. keep_aux != 0 writes the aux tags a BAM reader kept (pcabi_fastx_keep_aux): a
  *       part that is its whole read, with the read's bases as stored, gets them verbatim; any other
  *       part gets them without the position-dependent tags MM ML MN Mm Ml mv, which are dropped and
- *       not recomputed.
+ *       not recomputed. keep_aux = 2 recomputes MM ML MN Mm Ml instead (the block below); mv is
+ *       still dropped.
  *   pcabi_fastx_keep_aux : before the first pcabi_fastx_next, on = 1 makes a BAM reader keep every
  *       kept record's aux bytes and whether its bases are stored as written (not reverse-strand); any
  *       other input: no effect. A record whose aux chain does not walk (types A c C s S i I f Z H B)
@@ -948,6 +949,83 @@ int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, co
 int pcabi_fastx_keep_aux(pcabi_fastx *r, int on);
 int pcabi_reads_aux(const pcabi_reads *b, const uint8_t **aux, const int64_t **aux_off, const uint8_t **as_stored);
 int pcabi_fastx_bam_header(const pcabi_fastx *r, const char **text, int64_t *len);
+
+/* ---- base-modification tags remapped onto parts (csrc/pcabi_mods.h, csrc/pcabi_mods.hip) ------
+ * MM / ML / MN (SAMtags "Base modifications"; Mm / Ml are the older spellings) count occurrences of a
+ * base along the read, so a trimmed read or a split piece needs them recomputed. An MM group
+ * `base strand codes [flag] (,count)* ;` marks ordinals o0 = d0, ok = o(k-1) + 1 + dk among the
+ * occurrences of its base (U counts T, N counts every base) in the read as the reader returns it (a
+ * reverse-strand record already reverse-complemented). For a part [s0, s0 + ns) with c0 occurrences
+ * before its start and c1 before its end a group keeps the entries c0 <= ordinal < c1 and is written
+ * as its header, verbatim, then the kept counts -- the first as ordinal - c0, the others byte for byte
+ * as they stood -- then ';'; a group that keeps nothing is its header and ';'. ML (B:C, one value per
+ * entry per code) keeps the kept entries' values and is written whenever the read had one, MN whenever
+ * the read had one, as type i with value ns. A part's tag bytes are MM, ML, MN in this order, under
+ * the spellings they came in.
+ * A read's tags are usable when: the MM text is well formed; it has at most 32 groups; every count
+ * fits int32; in every group the last ordinal is below the read's count of that base; ML, if present,
+ * holds exactly sum(entries * codes) values; MN, if present, equals the read's length; and the caller
+ * found exactly one MM tag, of type Z, no ML without it, ML of type B:C, MN an integer
+ * (PCABI_MODS_BAD otherwise). The parts of a read that is not usable get no tag bytes (length 0).
+ *   pcabi_mods_read : one read that carries any of the tags. Its letters, its MM text (without the
+ *       NUL) and its ML values, as offsets into a sequence buffer and a tag blob; its parts are
+ *       parts[part0, part0 + n_parts).
+ *   pcabi_mods_part : [s0, s0 + ns) of read `read`; len = the length of its tag bytes, out = where
+ *       they go.
+ *   pcabi_mods_plan  : fills parts[].len and usable[0, n_reads) (1 usable, 0 not), and adds the reads
+ *       to the counters. device >= 0: the letters, the tag blob and the tables go up, the device
+ *       parses the MM text into ordinals, counts every group's base up to each part boundary and
+ *       selects each part's entries; the lengths and the flags come back. device < 0: the host build
+ *       of the same code (no GPU needed). A read or a part that points outside its buffers, or a part
+ *       outside its read's range of the table, is refused (PCABI_E_ARG).
+ *   pcabi_mods_remap : writes every part's tag bytes to out[part.out, part.out + part.len). parts[]
+ *       as pcabi_mods_plan left them, with out set; a len that is not what the plan gives, ranges that
+ *       overlap or an out outside out[0, out_cap) are refused (PCABI_E_ARG). On the device the output
+ *       lies between 64 guard bytes, checked after the kernel (PCABI_E_DEVICE if it wrote outside).
+ *       Bytes no part owns keep their values.
+ *   pcabi_mods_counts : reads remapped and reads whose modification tags were dropped (not usable),
+ *       as pcabi_mods_plan and pcabi_reads_write_bam(keep_aux = 2) counted them since the last call
+ *       with reset != 0.
+ *   pcabi_mods_last_times : ms[0..3] = milliseconds k_mods_plan and k_mods_write took (device events,
+ *       counted while pcabi_bam_last_times' profiling is on), the wall time of the host build
+ *       (device < 0, on the io threads) and the wall time of the device's sizing step (the tag blob
+ *       and the tables up, k_mods_plan, the lengths back, and whatever the stream still held);
+ *       *bytes = what the two kernels read and wrote; all since the last call with reset != 0.
+ * pcabi_reads_write_bam with keep_aux = 2 keeps the tags as keep_aux = 1 does and remaps these: a
+ * changed read's part (a trimmed read, a split piece, a read from a reverse-strand record) gets its
+ * other tags in file order, then MM, ML, MN by the rule above; a read whose tags are not usable loses
+ * MM ML MN Mm Ml from all its parts, as with keep_aux = 1. mv is dropped either way. With device >= 0
+ * the remap runs there before k_bam_pack, into the device copy of the side blob.
+ */
+#define PCABI_MODS_OLD_MM 1 /* the MM tag was spelled Mm */
+#define PCABI_MODS_BAD 2    /* the caller found the read's tags unusable */
+#define PCABI_MODS_OLD_ML 4 /* the ML tag was spelled Ml */
+typedef struct pcabi_mods_read {
+    int64_t seq_off; /* the read's letters in the sequence buffer, in the reader's orientation */
+    int64_t mm_off;  /* the MM text in the tag blob                                            */
+    int64_t ml_off;  /* the ML values in the tag blob                                          */
+    int64_t part0;   /* its parts in the part table                                            */
+    int32_t l_seq;
+    int32_t mm_len;  /* < 0: no MM tag                                                         */
+    int32_t ml_len;  /* < 0: no ML tag                                                         */
+    int32_t mn;      /* < 0: no MN tag                                                         */
+    int32_t n_parts;
+    int32_t flags;   /* PCABI_MODS_*                                                           */
+} pcabi_mods_read;
+typedef struct pcabi_mods_part {
+    int64_t out; /* where the tag bytes go                 */
+    int32_t read;
+    int32_t s0, ns;
+    int32_t len; /* the tag bytes' length (pcabi_mods_plan) */
+} pcabi_mods_part;
+int pcabi_mods_plan(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
+                    const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts, int64_t n_parts,
+                    uint8_t *usable);
+int pcabi_mods_remap(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
+                     const pcabi_mods_read *reads, int64_t n_reads, const pcabi_mods_part *parts, int64_t n_parts,
+                     uint8_t *out, int64_t out_cap);
+void pcabi_mods_counts(int reset, int64_t *remapped, int64_t *dropped);
+void pcabi_mods_last_times(int reset, double *ms, int64_t *bytes);
 
 #ifdef __cplusplus
 }
