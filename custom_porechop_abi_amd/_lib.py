@@ -154,6 +154,8 @@ def lib():
         'pcabi_bam_pack_last_times': ([c_int, c_p, c_p], None),
         'pcabi_reads_write_bam': ([c_p, ctypes.c_char_p, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p,
                                    ctypes.c_char_p, c_i64, c_int, c_int], c_int),
+        'pcabi_reads_write_bam_tags': ([c_p, ctypes.c_char_p, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p,
+                                        ctypes.c_char_p, c_i64, c_int, c_int, c_int], c_int),
         'pcabi_fastx_keep_aux': ([c_p, c_int], c_int),
         'pcabi_reads_aux': ([c_p, c_p, c_p, c_p], c_int),
         'pcabi_fastx_bam_header': ([c_p, c_p, c_p], c_int),
@@ -161,6 +163,10 @@ def lib():
         'pcabi_mods_remap': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
         'pcabi_mods_counts': ([c_int, c_p, c_p], None),
         'pcabi_mods_last_times': ([c_int, c_p, c_p], None),
+        'pcabi_moves_plan': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p], c_int),
+        'pcabi_moves_remap': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_moves_counts': ([c_int, c_p, c_p], None),
+        'pcabi_moves_last_times': ([c_int, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -204,7 +210,8 @@ def exported_symbols():
             'pcabi_bam_last_times', 'pcabi_bgzf_scratch_bytes', 'pcabi_bgzf_dev', 'pcabi_bam_pack_plan',
             'pcabi_bam_pack_dev', 'pcabi_bam_pack_host', 'pcabi_bam_pack_last_times', 'pcabi_reads_write_bam',
             'pcabi_fastx_keep_aux', 'pcabi_reads_aux', 'pcabi_fastx_bam_header', 'pcabi_mods_plan', 'pcabi_mods_remap',
-            'pcabi_mods_counts', 'pcabi_mods_last_times']
+            'pcabi_mods_counts', 'pcabi_mods_last_times', 'pcabi_moves_plan', 'pcabi_moves_remap', 'pcabi_moves_counts',
+            'pcabi_moves_last_times', 'pcabi_reads_write_bam_tags']
 
 
 class CrossRegion(ctypes.Structure):

@@ -151,8 +151,9 @@ struct Span {
 std::mutex g_prof_mu;
 bool g_prof = false;
 std::vector<Span *> g_spans;
-double g_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // [4]: k_bam_pack, [5]: k_mods_plan, [6]: k_mods_write
-int64_t g_unpack_bytes = 0, g_pack_bytes = 0, g_mods_bytes = 0;
+// [4]: k_bam_pack, [5]: k_mods_plan, [6]: k_mods_write, [7..10]: k_moves_count, its scan, k_moves_select, k_moves_write
+double g_ms[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+int64_t g_unpack_bytes = 0, g_pack_bytes = 0, g_mods_bytes = 0, g_moves_bytes = 0;
 
 void harvest() {   // g_prof_mu held; the spans' streams are idle
     for (Span *s : g_spans) {
@@ -176,7 +177,7 @@ bool prof_on() {
 }
 
 // kind: 0 k_inflate, 1 k_bam_unpack, 2 copies to the device, 3 copies from the device, 4 k_bam_pack,
-// 5 k_mods_plan, 6 k_mods_write
+// 5 k_mods_plan, 6 k_mods_write, 7 k_moves_count, 8 the move tables' scan, 9 k_moves_select and k_moves_size, 10 k_moves_write
 void *prof_begin(void *stream, int kind) {
     Span *s = new Span();
     s->kind = kind;
@@ -316,6 +317,7 @@ struct PackDev {
     PinBuf<> p_z;      // the compressed bytes, pinned
     Stream st;
     ModsDev *mods = nullptr;   // the remap's device side (pcabi_mods.hip), made at its first use
+    MovesDev *moves = nullptr; // the move tables' (pcabi_moves.hip), likewise
 };
 // kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
 // HIP runtime that may already have shut down
@@ -325,7 +327,7 @@ std::mutex g_pack_mu;
 
 namespace {
 int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, BamWriteJob job,
-                  const ModsTables *mods, const std::function<void(BamWriteJob *)> *layout,
+                  const ModsTables *mods, const MovesTables *moves, const std::function<void(BamWriteJob *)> *layout,
                   const std::function<void(const uint8_t *, int64_t)> &sink) {
     std::lock_guard<std::mutex> lk(g_pack_mu);
     if (device < 0) PCABI_TRY(hipGetDevice(&device));
@@ -333,6 +335,7 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
         (void)hipSetDevice(g_pack.device);
         g_pack.st.release();
         mods_dev_free(g_pack.mods);
+        moves_dev_free(g_pack.moves);
         g_pack = PackDev();
     }
     PCABI_TRY(hipSetDevice(device));
@@ -344,13 +347,22 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
     // the letters first: the remap counts them where the pack reads them
     if (int rc = g_pack.buf[0].reserve(seq_n + 64, std::max<int64_t>(seq_n + 64 + seq_n / 4, 1 << 20))) return rc;
     if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(g_pack.buf[0], seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
+    // the tags to remap are sized in one round trip: the move tables' stages are queued, the
+    // modification tags' plan runs behind them and waits for the stream, then the lengths are read
+    if (moves) {
+        if (!g_pack.moves) g_pack.moves = moves_dev_new();
+        if (int rc = moves_check(*moves)) return rc;
+        if (int rc = moves_dev_plan_begin(g_pack.moves, st, *moves)) return rc;
+    }
     if (mods) {
         if (!g_pack.mods) g_pack.mods = mods_dev_new();
         if (int rc = mods_plan_any(device, g_pack.mods, nullptr, st, seq, g_pack.buf[0], seq_n, mods->tags, mods->tags_n, mods->reads,
                                    mods->n_reads, mods->parts, mods->n_parts, mods->usable))
             return rc;
-        (*layout)(&job);
     }
+    if (moves)
+        if (int rc = moves_dev_plan_end(g_pack.moves, st, *moves)) return rc;
+    if (mods || moves) (*layout)(&job);
     const uint8_t *head = job.head, *side = job.side;
     const pcabi_bam_part *parts = job.parts;
     const int64_t head_n = job.head_n, side_n = job.side_n, n_parts = job.n_parts, n_tiles = job.n_tiles, stream_n = job.stream_n;
@@ -374,6 +386,8 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
     if (head_n > 0) PCABI_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
     if (mods)
         if (int rc = mods_dev_write(g_pack.mods, st, mods->parts, mods->n_parts, d_side, side_n)) return rc;
+    if (moves)
+        if (int rc = moves_dev_write(g_pack.moves, st, moves->parts, moves->n_parts, d_side, side_n)) return rc;
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 4) : nullptr;
     if (int rc = launch_pack(st, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, n_tiles, d_stream, stream_n))
@@ -404,18 +418,19 @@ int64_t bam_write_dev(int device, const uint8_t *head, int64_t head_n, const uin
     BamWriteJob job;
     job.head = head, job.head_n = head_n, job.side = side, job.side_n = side_n;
     job.parts = parts, job.n_parts = n_parts, job.n_tiles = n_tiles, job.stream_n = stream_n;
-    return write_dev(device, seq, seq_n, qual, qual_n, job, nullptr, nullptr, sink);
+    return write_dev(device, seq, seq_n, qual, qual_n, job, nullptr, nullptr, nullptr, sink);
 }
 
-int64_t bam_write_mods_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables &mods,
-                           const std::function<void(BamWriteJob *)> &layout,
+int64_t bam_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables *mods,
+                           const MovesTables *moves, const std::function<void(BamWriteJob *)> &layout,
                            const std::function<void(const uint8_t *, int64_t)> &sink) {
-    return write_dev(device, seq, seq_n, qual, qual_n, BamWriteJob(), &mods, &layout, sink);
+    return write_dev(device, seq, seq_n, qual, qual_n, BamWriteJob(), mods, moves, &layout, sink);
 }
 
 void prof_add_bytes(int kind, int64_t bytes) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     if (kind == 5 || kind == 6) g_mods_bytes += bytes;
+    if (kind >= 7 && kind <= 10) g_moves_bytes += bytes;
 }
 
 }  // namespace pcabi_internal
@@ -625,6 +640,19 @@ void pcabi_mods_last_times(int reset, double *ms, int64_t *bytes) {
     if (reset) {
         g_ms[5] = g_ms[6] = 0;
         g_mods_bytes = 0;
+    }
+}
+
+void pcabi_moves_last_times(int reset, double *ms, int64_t *bytes) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    harvest();
+    int64_t dev_ns = 0;
+    const int64_t host_ns = moves_host_ns(reset, &dev_ns);
+    if (ms) ms[0] = g_ms[7], ms[1] = g_ms[8], ms[2] = g_ms[9], ms[3] = g_ms[10], ms[4] = 1e-6 * (double)host_ns, ms[5] = 1e-6 * (double)dev_ns;
+    if (bytes) *bytes = g_moves_bytes;
+    if (reset) {
+        g_ms[7] = g_ms[8] = g_ms[9] = g_ms[10] = 0;
+        g_moves_bytes = 0;
     }
 }
 

@@ -1,5 +1,5 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
 // the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
 // pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
 // compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
@@ -197,10 +197,22 @@ struct ModsTables {
     int64_t n_parts = 0;
     uint8_t *usable = nullptr;
 };
-int64_t bam_write_mods_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables &mods,
-                           const std::function<void(BamWriteJob *)> &layout,
+// the move tables to remap (pcabi_moves.hip): the tag blob, the tables, the reads' flags
+struct MovesTables {
+    const uint8_t *tags = nullptr;
+    int64_t tags_n = 0;
+    const pcabi_moves_read *reads = nullptr;
+    int64_t n_reads = 0;
+    pcabi_moves_part *parts = nullptr;
+    int64_t n_parts = 0;
+    uint8_t *usable = nullptr;
+};
+// mods and moves: either may be null, not both; the two are sized in one round trip before `layout` runs
+int64_t bam_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables *mods,
+                           const MovesTables *moves, const std::function<void(BamWriteJob *)> &layout,
                            const std::function<void(const uint8_t *, int64_t)> &sink);
-void prof_add_bytes(int kind, int64_t bytes);   // 5 k_mods_plan, 6 k_mods_write
+// 5 k_mods_plan, 6 k_mods_write; 7 the move tables' sizing stages, 10 k_moves_write
+void prof_add_bytes(int kind, int64_t bytes);
 
 // ---- pcabi_io.cpp --------------------------------------------------------------------------------
 int io_thread_count();
@@ -226,5 +238,27 @@ ModsDev *mods_dev_new();
 // wall time the host build took, and the device plan step (copies up, kernel, lengths back): pcabi_mods_last_times
 int64_t mods_host_ns(int reset, int64_t *dev_plan_ns);
 void mods_dev_free(ModsDev *d);   // its device current
+
+
+// ---- pcabi_moves.hip -----------------------------------------------------------------------------
+// the device half of the move-table remap: the tag blob, the tables, the segment prefixes and every
+// part boundary's move of the plan before
+struct MovesDev;
+// the host build's part boundaries, kept from its sizing pass for its writing pass
+struct MovesHost;
+int moves_check(const MovesTables &t);   // the tables against the blob and each other (PCABI_E_ARG)
+// the host build: checks the tables, fills parts[].len and usable[], counts the reads; then the bytes
+int moves_plan_host(MovesHost *keep, const MovesTables &t);
+void moves_write_host(MovesHost *keep, const MovesTables &t, uint8_t *out);
+// the device: begin queues the sizing on `stream` (tables checked before), end waits and fills
+// parts[].len and usable[] and counts; write fills the parts' bytes into d_out, asynchronous
+int moves_dev_plan_begin(MovesDev *d, void *stream, const MovesTables &t);
+int moves_dev_plan_end(MovesDev *d, void *stream, const MovesTables &t);
+int moves_dev_write(MovesDev *d, void *stream, const pcabi_moves_part *parts, int64_t n_parts, uint8_t *d_out, int64_t out_cap);
+MovesHost *moves_host_new();
+void moves_host_free(MovesHost *h);
+MovesDev *moves_dev_new();
+void moves_dev_free(MovesDev *d);   // its device current
+int64_t moves_host_ns(int reset, int64_t *dev_plan_ns);   // pcabi_moves_last_times
 
 }  // namespace pcabi_internal

@@ -1786,13 +1786,68 @@ int64_t mods_read_of(const uint8_t *aux, int64_t a0, int64_t a1, int64_t seq_off
     return (int64_t)reads->size() - 1;
 }
 
+// an integer tag's value (types c C s S i I), or INT64_MIN for any other type
+int64_t aux_int(const uint8_t *tg) {
+    using namespace pcabi_bam;
+    switch (tg[2]) {
+        case 'c': return (int8_t)tg[3];
+        case 'C': return tg[3];
+        case 's': return (int16_t)le16(tg + 3);
+        case 'S': return le16(tg + 3);
+        case 'i': return le32(tg + 3);
+        case 'I': return (uint32_t)le32(tg + 3);
+        default: return INT64_MIN;
+    }
+}
+
+// The move table of one read's aux chain (include/pcabi.h pcabi_moves_read): -1 when it carries no mv
+// tag; else its entry appended to *reads. What only the chain can tell -- mv twice or not of type B:c /
+// B:C, ts twice, not an integer, negative or above INT32_MAX -- marks the read PCABI_MOVES_BAD.
+int64_t moves_read_of(const uint8_t *aux, int64_t a0, int64_t a1, int64_t l_seq, std::vector<pcabi_moves_read> *reads, int64_t part0) {
+    using namespace pcabi_bam;
+    const uint8_t *ax = aux + a0;
+    const int64_t an = a1 - a0;
+    pcabi_moves_read r;
+    std::memset(&r, 0, sizeof r);
+    r.part0 = part0, r.l_seq = (int32_t)l_seq, r.ts = -1;
+    int n_mv = 0, n_ts = 0;
+    for (int64_t at = 0; at < an;) {
+        const int64_t nx = aux_next(ax, an, at);
+        if (nx < 0) break;
+        const uint8_t *tg = ax + at;
+        if (tg[0] == 'm' && tg[1] == 'v') {
+            const uint32_t count = tg[2] == 'B' ? (uint32_t)le32(tg + 4) : 0;
+            if (++n_mv > 1 || tg[2] != 'B' || (tg[3] != 'c' && tg[3] != 'C') || count > (uint32_t)INT32_MAX - 64) r.flags |= PCABI_MOVES_BAD;
+            else r.mv_off = a0 + at + 8, r.n_vals = (int32_t)count;
+        } else if (tg[0] == 't' && tg[1] == 's') {
+            const int64_t v = aux_int(tg);
+            if (++n_ts > 1 || v < 0 || v > INT32_MAX) r.flags |= PCABI_MOVES_BAD;
+            else r.ts = (int32_t)v;
+        }
+        at = nx;
+    }
+    if (n_mv == 0) return -1;
+    if (r.flags & PCABI_MOVES_BAD) r.mv_off = 0, r.n_vals = 0;
+    reads->push_back(r);
+    return (int64_t)reads->size() - 1;
+}
+
 }  // namespace
 
 extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
                                      const int32_t *end_trim, const int64_t *cut_off, const int64_t *cuts,
                                      int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
                                      const char *header_text, int64_t header_len, int keep_aux, int device) {
+    return pcabi_reads_write_bam_tags(b, path, append, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed,
+                                      select, header_text, header_len, keep_aux, 0, device);
+}
+
+extern "C" int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
+                                          const int32_t *end_trim, const int64_t *cut_off, const int64_t *cuts,
+                                          int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
+                                          const char *header_text, int64_t header_len, int keep_aux, int tag_flags, int device) {
     using namespace pcabi_bam;
+    if (tag_flags & ~PCABI_BAM_KEEP_MOVES) return fail(PCABI_E_ARG, "unknown tag_flags");
     if (!b || !path || header_len < 0 || header_len > INT32_MAX - 16 || (header_len > 0 && !header_text))
         return fail(PCABI_E_ARG, "bad arguments");
     if (std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "BAM output goes to files, not stdout");
@@ -1801,6 +1856,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
     const bool have_aux = keep_aux && !b->aux_off.empty();
     const bool remap = have_aux && keep_aux == 2;
+    const bool keep_moves = have_aux && (tag_flags & PCABI_BAM_KEEP_MOVES);
     const bool no_qual = b->type == PCABI_FASTA;
     const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
     // A part keeps its read's aux bytes verbatim when it is the whole read with the bases as stored.
@@ -1813,25 +1869,56 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     std::vector<pcabi_mods_part> mparts;
     std::vector<int64_t> mpart0((size_t)nt + 1, 0);   // a thread's first entry of mparts
     std::vector<uint8_t> has_mods(remap ? (size_t)b->n : 0, 0);
-    if (remap) {
+    // the same for the move tables (pcabi_moves_*): vread[i] = the read's entry of vreads, -1 without one
+    std::vector<pcabi_moves_read> vreads;
+    std::vector<pcabi_moves_part> vparts;
+    std::vector<int64_t> vpart0((size_t)nt + 1, 0);
+    std::vector<int32_t> vread(keep_moves ? (size_t)b->n : 0, -1);
+    if (remap || keep_moves) {
         std::vector<std::vector<pcabi_mods_read>> t_reads((size_t)nt);
         std::vector<std::vector<pcabi_mods_part>> t_parts((size_t)nt);
+        std::vector<std::vector<pcabi_moves_read>> t_vreads((size_t)nt);
+        std::vector<std::vector<pcabi_moves_part>> t_vparts((size_t)nt);
         fan_out(nt, [&](int t) {
             std::vector<std::pair<int64_t, int64_t>> rg;
             for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
-                int64_t mread = -2;   // the read's entry; -1: it carries none of the tags; -2: not looked yet
+                int64_t mread = -2, mv = -2;   // the read's entry; -1: it carries none of the tags; -2: not looked yet
                 read_parts(wa, i, rg, [&](const char *, size_t, bool own, int64_t s0, int64_t ns, int64_t, int64_t) {
                     if (verbatim(i, own, s0, ns)) return;
-                    if (mread == -2)
+                    if (remap && mread == -2)
                         mread = mods_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i],
                                              b->seq_off[i + 1] - b->seq_off[i], &t_reads[(size_t)t], (int64_t)t_parts[(size_t)t].size());
-                    if (mread < 0) return;
+                    if (keep_moves && mv == -2)
+                        mv = moves_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i + 1] - b->seq_off[i],
+                                           &t_vreads[(size_t)t], (int64_t)t_vparts[(size_t)t].size());
+                    if (keep_moves && mv >= 0) {
+                        vread[(size_t)i] = (int32_t)mv;
+                        ++t_vreads[(size_t)t][(size_t)mv].n_parts;
+                        t_vparts[(size_t)t].push_back(pcabi_moves_part{0, (int32_t)mv, (int32_t)s0, (int32_t)ns, 0});
+                    }
+                    if (!remap || mread < 0) return;
                     has_mods[(size_t)i] = 1;
                     ++t_reads[(size_t)t][(size_t)mread].n_parts;
                     t_parts[(size_t)t].push_back(pcabi_mods_part{0, (int32_t)mread, (int32_t)s0, (int32_t)ns, 0});
                 });
             }
         });
+        for (int t = 0; t < nt; ++t) {
+            const int64_t read_base = (int64_t)vreads.size(), part_base = (int64_t)vparts.size();
+            vpart0[(size_t)t] = part_base;
+            for (pcabi_moves_read r : t_vreads[(size_t)t]) {
+                r.part0 += part_base;
+                vreads.push_back(r);
+            }
+            for (pcabi_moves_part p : t_vparts[(size_t)t]) {
+                p.read += (int32_t)read_base;
+                vparts.push_back(p);
+            }
+            if (keep_moves)
+                for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i)
+                    if (vread[(size_t)i] >= 0) vread[(size_t)i] += (int32_t)read_base;
+        }
+        vpart0[(size_t)nt] = (int64_t)vparts.size();
         for (int t = 0; t < nt; ++t) {
             const int64_t read_base = (int64_t)mreads.size(), part_base = (int64_t)mparts.size();
             mpart0[(size_t)t] = part_base;
@@ -1851,13 +1938,19 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
     pcabi_internal::ModsTables mt;
     mt.tags = b->aux.data(), mt.tags_n = (int64_t)b->aux.size(), mt.reads = mreads.data(), mt.n_reads = (int64_t)mreads.size();
     mt.parts = mparts.data(), mt.n_parts = (int64_t)mparts.size(), mt.usable = usable.data();
+    const bool moves = !vreads.empty();
+    std::vector<uint8_t> vusable(vreads.size());
+    pcabi_internal::MovesTables vt;
+    vt.tags = b->aux.data(), vt.tags_n = (int64_t)b->aux.size(), vt.reads = vreads.data(), vt.n_reads = (int64_t)vreads.size();
+    vt.parts = vparts.data(), vt.n_parts = (int64_t)vparts.size(), vt.usable = vusable.data();
     std::vector<pcabi_bam_part> parts;
     std::vector<uint8_t> side, head;
     int64_t emitted = 0, stream_n = 0;
     PackLayout lay;
     // The parts and their side blob (name, then aux bytes), per thread's range of reads, then joined, and the
     // chain planned. With sized modification tags (mparts[].len) a gap of the tags' length follows a part's
-    // kept tags, and mparts[].out names it.
+    // kept tags, and mparts[].out names it; a gap for a sized move table (vparts[].len, mv then ts) follows
+    // that, and a read whose ts is rewritten there loses it from the kept tags.
     auto layout = [&] {
         std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
         std::vector<std::vector<uint8_t>> t_side((size_t)nt);
@@ -1866,7 +1959,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
             std::vector<std::pair<int64_t, int64_t>> rg;
             std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
             std::vector<uint8_t> &side = t_side[(size_t)t];
-            int64_t mp = mpart0[(size_t)t];
+            int64_t mp = mpart0[(size_t)t], vp = vpart0[(size_t)t];
             for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
                 t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
                     pcabi_bam_part p;
@@ -1887,16 +1980,24 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
                         if (verbatim(i, own, s0, ns)) {
                             side.insert(side.end(), ax, ax + an);   // the whole read, as stored
                         } else {   // a changed read: without the tags that count its bases
+                            const int32_t vr = keep_moves ? vread[(size_t)i] : -1;
+                            const bool new_ts = vr >= 0 && vusable[(size_t)vr] && vreads[(size_t)vr].ts >= 0;
                             for (int64_t at = 0; at < an;) {
                                 const int64_t nx = aux_next(ax, an, at);
                                 if (nx < 0) break;
-                                if (!aux_positional(ax + at)) side.insert(side.end(), ax + at, ax + nx);
+                                if (!aux_positional(ax + at) && !(new_ts && ax[at] == 't' && ax[at + 1] == 's'))
+                                    side.insert(side.end(), ax + at, ax + nx);
                                 at = nx;
                             }
                             if (remap && has_mods[(size_t)i]) {   // its remapped tags go behind them
                                 mparts[(size_t)mp].out = (int64_t)side.size();
                                 side.resize(side.size() + (size_t)mparts[(size_t)mp].len);
                                 ++mp;
+                            }
+                            if (vr >= 0) {   // and its move table behind those
+                                vparts[(size_t)vp].out = (int64_t)side.size();
+                                side.resize(side.size() + (size_t)vparts[(size_t)vp].len);
+                                ++vp;
                             }
                         }
                         p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
@@ -1912,6 +2013,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
                 parts.push_back(p);
             }
             for (int64_t m = mpart0[(size_t)t]; m < mpart0[(size_t)t + 1]; ++m) mparts[(size_t)m].out += base;
+            for (int64_t m = vpart0[(size_t)t]; m < vpart0[(size_t)t + 1]; ++m) vparts[(size_t)m].out += base;
             side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
             t_side[(size_t)t] = std::vector<uint8_t>();
             emitted += t_emit[(size_t)t];
@@ -1929,7 +2031,7 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
         for (pcabi_bam_part &p : parts) lay.place(&p);
         stream_n = lay.out;
     };
-    if (!mods) layout();   // nothing to size first
+    if (!mods && !moves) layout();   // nothing to size first
     const int64_t seq_n = (int64_t)b->seq.size(), qual_n = (int64_t)b->qual.size();
     // the file: opened before anything is compressed, written in large write() calls
     const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
@@ -1945,8 +2047,9 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
         const double t0 = now_s();
         double layout_s = 0;   // the side blob and the chain, built inside the device call once the tags are sized
         int64_t zn = 0;
-        if (mods) {
-            zn = pcabi_internal::bam_write_mods_dev(device, (const uint8_t *)b->seq.data(), seq_n, (const uint8_t *)b->qual.data(), qual_n, mt,
+        if (mods || moves) {
+            zn = pcabi_internal::bam_write_tags_dev(device, (const uint8_t *)b->seq.data(), seq_n, (const uint8_t *)b->qual.data(), qual_n,
+                                                    mods ? &mt : nullptr, moves ? &vt : nullptr,
                                                     [&](pcabi_internal::BamWriteJob *job) {
                                                         const double t1 = now_s();
                                                         layout();
@@ -1978,10 +2081,25 @@ extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int
                 ::close(fd);
                 return rc;
             }
-            layout();
+        }
+        pcabi_internal::MovesHost *vkeep = moves ? pcabi_internal::moves_host_new() : nullptr;
+        if (moves) {
+            if (const int rc = pcabi_internal::moves_plan_host(vkeep, vt)) {
+                pcabi_internal::moves_host_free(vkeep);
+                if (keep) pcabi_internal::mods_host_free(keep);
+                ::close(fd);
+                return rc;
+            }
+        }
+        if (mods || moves) layout();
+        if (mods) {
             pcabi_internal::mods_write_host(keep, (const uint8_t *)b->seq.data(), mt.tags, mt.reads, mt.n_reads, mt.parts, mt.n_parts,
                                             side.data());
             pcabi_internal::mods_host_free(keep);
+        }
+        if (moves) {
+            pcabi_internal::moves_write_host(vkeep, vt, side.data());
+            pcabi_internal::moves_host_free(vkeep);
         }
         std::vector<uint8_t, NoInit<uint8_t>> stream;
         stream.resize((size_t)stream_n);

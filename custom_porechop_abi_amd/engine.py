@@ -883,3 +883,56 @@ def mods_counts(reset=False):
     v = np.zeros(2, np.int64)
     lib().pcabi_mods_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
     return int(v[0]), int(v[1])
+
+
+# ---- move tables remapped onto parts (csrc/pcabi_moves.h, csrc/pcabi_moves.hip) ---------------------
+# include/pcabi.h pcabi_moves_read (40 bytes: 4 of padding at its end), pcabi_moves_part
+MOVES_READ = np.dtype([('mv_off', np.int64), ('part0', np.int64), ('l_seq', np.int32), ('n_vals', np.int32), ('ts', np.int32),
+                       ('n_parts', np.int32), ('flags', np.int32)], align=True)
+MOVES_PART = np.dtype([('out', np.int64), ('read', np.int32), ('s0', np.int32), ('ns', np.int32), ('len', np.int32)])
+MOVES_BAD = 1
+assert MOVES_READ.itemsize == 40 and MOVES_PART.itemsize == 24
+
+
+def _moves_args(tags, reads, name):
+    tags = np.ascontiguousarray(np.frombuffer(tags, np.uint8) if isinstance(tags, (bytes, bytearray)) else tags, np.uint8)
+    if reads.dtype != MOVES_READ or not reads.flags['C_CONTIGUOUS']:
+        raise ValueError('%s: reads is a C-contiguous MOVES_READ array' % name)
+    return tags
+
+
+def moves_plan(tags, reads, parts, device=0):
+    """The lengths of every part's remapped mv / ts tag bytes and which reads' move tables are usable
+    (pcabi_moves_plan): on GPU `device`, or with the host build of the same code when device < 0. tags:
+    the bytes the MOVES_READ array `reads` indexes (mv_off: a table's first value, its stride); parts: a
+    C-contiguous MOVES_PART array with read / s0 / ns set, whose 'len' is filled in place. Returns
+    (parts, usable uint8 [n_reads])."""
+    tags = _moves_args(tags, reads, 'moves_plan')
+    if parts.dtype != MOVES_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('moves_plan: parts is a C-contiguous MOVES_PART array')
+    usable = np.zeros(reads.size, np.uint8)
+    rc = lib().pcabi_moves_plan(int(device), _ptr(tags), tags.size, _ptr(reads), reads.size, _ptr(parts), parts.size, _ptr(usable))
+    check(int(rc), 'pcabi_moves_plan')
+    return parts, usable
+
+
+def moves_remap(tags, reads, parts, out, device=0):
+    """Every part's tag bytes (mv, then ts) written to out[part.out, part.out + part.len)
+    (pcabi_moves_remap): parts as moves_plan left them, with 'out' set; out: a C-contiguous uint8 array,
+    filled in place (bytes no part owns keep their values) and returned."""
+    tags = _moves_args(tags, reads, 'moves_remap')
+    parts = np.ascontiguousarray(parts, MOVES_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('moves_remap: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_moves_remap(int(device), _ptr(tags), tags.size, _ptr(reads), reads.size, _ptr(parts), parts.size, _ptr(out),
+                                 out.size)
+    check(int(rc), 'pcabi_moves_remap')
+    return out
+
+
+def moves_counts(reset=False):
+    """(reads whose move table was remapped, reads whose mv was dropped as not usable) since the last
+    reset (pcabi_moves_counts)."""
+    v = np.zeros(2, np.int64)
+    lib().pcabi_moves_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
+    return int(v[0]), int(v[1])

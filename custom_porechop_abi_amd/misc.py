@@ -53,6 +53,8 @@ def _declare(L):
         'pcabi_bgzf_write_eof': ([ctypes.c_char_p], c_int),
         'pcabi_reads_write_bam': ([P, ctypes.c_char_p, c_int, P, P, P, P, c_int, c_int, c_int, P, ctypes.c_char_p, i64,
                                    c_int, c_int], c_int),
+        'pcabi_reads_write_bam_tags': ([P, ctypes.c_char_p, c_int, P, P, P, P, c_int, c_int, c_int, P, ctypes.c_char_p,
+                                        i64, c_int, c_int, c_int], c_int),
         'pcabi_fastx_keep_aux': ([P, c_int], c_int),
         'pcabi_reads_aux': ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)], c_int),
         'pcabi_fastx_bam_header': ([P, ctypes.POINTER(P), ctypes.POINTER(i64)], c_int),
@@ -527,7 +529,8 @@ def get_albacore_barcode_from_path(albacore_path):
 
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
-                cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False, keep_mods=False):
+                cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False, keep_mods=False,
+                keep_moves=False):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
     gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
@@ -545,8 +548,12 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     and as stored, without the position-dependent tags MM ML MN Mm Ml mv (dropped, not recomputed) for
     a trimmed read, a split piece or a read from a reverse-strand record. keep_mods (with keep_aux):
     MM ML MN Mm Ml are recomputed for such a read instead (include/pcabi.h "base-modification tags"),
-    on gzip_device when it is given; a read whose tags are not usable loses them as before, and mv is
-    dropped either way. engine.mods_counts() tells how many reads went which way.
+    on gzip_device when it is given; a read whose tags are not usable loses them as before.
+    engine.mods_counts() tells how many reads went which way. keep_moves (with keep_aux, independent of
+    keep_mods; pcabi_reads_write_bam_tags): such a read's move table mv is cut to each part and its ts
+    moved along (include/pcabi.h "move tables"), behind the other tags and MM ML MN; a read whose table
+    is not usable loses mv as before and keeps its ts; engine.moves_counts() tells how many went which
+    way. Direct-RNA move tables (which run against the sequence) and the sp / pi tags are not handled.
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -577,8 +584,18 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
         raise ValueError("bgzf applies to a '.gz' format compressed on a device (gzip_device)")
     if keep_mods and not (keep_aux and out_format == 'bam'):
         raise ValueError("keep_mods applies to out_format 'bam' with keep_aux")
+    if keep_moves and not (keep_aux and out_format == 'bam'):
+        raise ValueError("keep_moves applies to out_format 'bam' with keep_aux")
     if out_format == 'bam':
         hdr = None if bam_header is None else bytes(bam_header)
+        if keep_moves:
+            rc = L.pcabi_reads_write_bam_tags(batch._h, os.fsencode(path), int(append), p(st), p(et), p(co), p(cu),
+                                              int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel), hdr,
+                                              0 if hdr is None else len(hdr), 2 if keep_mods else 1, 1,
+                                              -1 if gzip_device is None else int(gzip_device))
+            if rc < 0:
+                check(rc, 'pcabi_reads_write_bam_tags')
+            return int(rc)
         rc = L.pcabi_reads_write_bam(batch._h, os.fsencode(path), int(append), p(st), p(et), p(co), p(cu),
                                      int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel), hdr,
                                      0 if hdr is None else len(hdr), 2 if keep_mods else int(bool(keep_aux)),

@@ -43,12 +43,13 @@ def _finish_mode(trimmer, out_format):
 
 def _bam_kw(trimmer, out_format, b):
     """misc.write_reads' BAM arguments for batch b: the input's header text when it was BAM, and the
-    trimmer's keep_tags and keep_mods."""
+    trimmer's keep_tags, keep_mods and keep_moves."""
     if out_format != 'bam':
         return {}
     keep = bool(getattr(trimmer, 'keep_tags', False))
     return {'bam_header': getattr(b, 'bam_header', None), 'keep_aux': keep,
-            'keep_mods': keep and bool(getattr(trimmer, 'keep_mods', False))}
+            'keep_mods': keep and bool(getattr(trimmer, 'keep_mods', False)),
+            'keep_moves': keep and bool(getattr(trimmer, 'keep_moves', False))}
 
 
 class FileTrimmer(object):
@@ -65,6 +66,7 @@ class FileTrimmer(object):
     gunzip_device = None                  # gzip inputs through zlib on the host (set by __init__)
     keep_tags = False                     # BAM to BAM: aux tags are dropped (set by __init__)
     keep_mods = False                     # with keep_tags: MM ML MN of changed reads are dropped, not remapped
+    keep_moves = False                    # with keep_tags: mv of changed reads is dropped, ts copied
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
@@ -72,17 +74,22 @@ class FileTrimmer(object):
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
-                 keep_mods=False):
+                 keep_mods=False, keep_moves=False):
         self.L = L = lib()
         # out_format 'bam' from a BAM input: the records' aux tags are read and written (misc.write_reads
         # keep_aux: verbatim on reads written whole and as stored, without the position-dependent tags
         # MM ML MN Mm Ml mv, which are dropped and not recomputed, on changed reads)
         self.keep_tags = bool(keep_tags)
         # keep_mods: MM ML MN Mm Ml of a changed read are recomputed for each part it is written as
-        # (misc.write_reads keep_mods), the bins' writers included; mv is still dropped
+        # (misc.write_reads keep_mods), the bins' writers included
         if keep_mods and not keep_tags:
             raise ValueError('keep_mods needs keep_tags')
         self.keep_mods = bool(keep_mods)
+        # keep_moves: mv of a changed read is cut to each part it is written as and ts moved along
+        # (misc.write_reads keep_moves), the bins' writers included
+        if keep_moves and not keep_tags:
+            raise ValueError('keep_moves needs keep_tags')
+        self.keep_moves = bool(keep_moves)
         self.device = int(device)
         # '.gz' output formats: zlib on the host (default) or the device encoder (misc.write_reads)
         self.gzip_device = self.device if gzip_on_device else None

@@ -912,8 +912,8 @@ void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
  *       same bytes. keep_aux != 0 writes the aux tags a BAM reader kept (pcabi_fastx_keep_aux): a
  *       part that is its whole read, with the read's bases as stored, gets them verbatim; any other
  *       part gets them without the position-dependent tags MM ML MN Mm Ml mv, which are dropped and
- *       not recomputed. keep_aux = 2 recomputes MM ML MN Mm Ml instead (the block below); mv is
- *       still dropped.
+ *       not recomputed. keep_aux = 2 recomputes MM ML MN Mm Ml instead (the block below); mv and
+ *       ts are remapped by pcabi_reads_write_bam_tags ("move tables" below), here mv is dropped.
  *   pcabi_fastx_keep_aux : before the first pcabi_fastx_next, on = 1 makes a BAM reader keep every
  *       kept record's aux bytes and whether its bases are stored as written (not reverse-strand); any
  *       other input: no effect. A record whose aux chain does not walk (types A c C s S i I f Z H B)
@@ -994,7 +994,7 @@ int pcabi_fastx_bam_header(const pcabi_fastx *r, const char **text, int64_t *len
  * pcabi_reads_write_bam with keep_aux = 2 keeps the tags as keep_aux = 1 does and remaps these: a
  * changed read's part (a trimmed read, a split piece, a read from a reverse-strand record) gets its
  * other tags in file order, then MM, ML, MN by the rule above; a read whose tags are not usable loses
- * MM ML MN Mm Ml from all its parts, as with keep_aux = 1. mv is dropped either way. With device >= 0
+ * MM ML MN Mm Ml from all its parts, as with keep_aux = 1. mv: see "move tables" below. With device >= 0
  * the remap runs there before k_bam_pack, into the device copy of the side blob.
  */
 #define PCABI_MODS_OLD_MM 1 /* the MM tag was spelled Mm */
@@ -1026,6 +1026,82 @@ int pcabi_mods_remap(int device, const uint8_t *seq, int64_t seq_n, const uint8_
                      uint8_t *out, int64_t out_cap);
 void pcabi_mods_counts(int reset, int64_t *remapped, int64_t *dropped);
 void pcabi_mods_last_times(int reset, double *ms, int64_t *bytes);
+
+/* ---- move tables remapped onto parts (csrc/pcabi_moves.h, csrc/pcabi_moves.hip) ---------------
+ * mv is the basecaller's move table, a B:c array (B:C is accepted): the stride S, then n moves of 0 or
+ * 1, each covering S samples of the signal; a 1 starts a base. ts is the number of samples trimmed
+ * before the read; the moves count from it. With `ones` the number of 1s, p(k) the index of the k-th 1
+ * (from 0) and p(ones) = n, a part [s0, s0 + ns) of the read, in the orientation the reader returns it
+ * (nothing is reversed for a reverse-strand record), takes the moves [q0, q1): q0 = 0 when s0 == 0
+ * (blocks before the first base stay with a part that starts the read), else p(s0); q1 = p(s0 + ns).
+ * Its tag bytes are `mv B c`, the count 1 + q1 - q0, S and the slice byte for byte (subtype c whatever
+ * came in), then, when the read had a ts tag, `ts i` with ts + S * q0. Ascending parts that tile the
+ * read concatenate to the original moves, and each slice holds ns ones.
+ * A read's table is usable when: there is exactly one mv tag, of type B:c or B:C (PCABI_MOVES_BAD
+ * otherwise); it has at least one value; 1 <= S <= 127; every move is 0 or 1; ones == l_seq; its ts, if
+ * any, is one integer tag (c C s S i I) with a value >= 0 (PCABI_MOVES_BAD otherwise: negative, another
+ * type, or twice), and ts + S * q0 <= INT32_MAX for all its parts. The first move need not be 1. The
+ * parts of a read that is not usable get no tag bytes (length 0). A table of more than INT32_MAX - 64
+ * values is refused (no BAM record holds one).
+ * Out of scope: direct-RNA files, whose move tables run against the sequence without the record saying
+ * so; the sp and pi tags of split reads; tags in FASTQ header comments. ns (the sample count before
+ * trimming) does not depend on the position and stays with the other tags.
+ *   pcabi_moves_read : one read with an mv tag: mv_off = the first value of the array (the stride) in
+ *       the tag blob, n_vals = how many values (stride included), ts < 0 = no ts tag; its parts are
+ *       parts[part0, part0 + n_parts).
+ *   pcabi_moves_part : [s0, s0 + ns) of read `read`; len = the length of its tag bytes (mv, then ts),
+ *       out = where they go.
+ *   pcabi_moves_plan  : fills parts[].len and usable[0, n_reads) and adds the reads to the counters.
+ *       device >= 0: the tag blob and the tables go up; k_moves_count counts the ones of fixed 4096-move
+ *       segments of all reads (16 bytes a lane a load, any alignment), a device scan turns the counts
+ *       into prefixes, k_moves_select finds each part boundary's move (a binary search over the read's
+ *       segments, then 64 bytes a pass with a ballot), k_moves_size decides usability and sizes the
+ *       parts; 4 bytes a part and one a read come back. device < 0: the host build of the same code (no
+ *       GPU needed). Tables that point outside their buffers are refused (PCABI_E_ARG).
+ *   pcabi_moves_remap : writes every part's tag bytes to out[part.out, part.out + part.len); refusals
+ *       and the 64 guard bytes on the device as for pcabi_mods_remap. Bytes no part owns keep their
+ *       values.
+ *   pcabi_moves_counts : reads remapped and reads whose mv was dropped (not usable) since the last call
+ *       with reset != 0.
+ *   pcabi_moves_last_times : ms[0..5] = milliseconds of k_moves_count, the scan, k_moves_select with
+ *       k_moves_size, and k_moves_write (device events, counted while pcabi_bam_last_times' profiling
+ *       is on), the wall time of the host build (device < 0, on the io threads) and the wall time of
+ *       the device's sizing step (blob and tables up, the three stages, the lengths back); *bytes = what
+ *       the kernels read and wrote; all since the last call with reset != 0.
+ * pcabi_reads_write_bam_tags is pcabi_reads_write_bam with tag_flags: PCABI_BAM_KEEP_MOVES (with
+ * keep_aux != 0) gives every changed part of a usable read its mv and its rewritten ts, behind the
+ * other tags in file order (without ts when it is rewritten) and behind MM ML MN when keep_aux = 2; a
+ * read that is not usable loses mv from its changed parts and keeps ts verbatim. tag_flags = 0 writes
+ * what pcabi_reads_write_bam writes. With device >= 0 the move tables are sized in the same round trip
+ * as the modification tags and written into the device copy of the side blob before k_bam_pack.
+ */
+#define PCABI_MOVES_BAD 1      /* the caller found the read's mv or ts unusable */
+#define PCABI_BAM_KEEP_MOVES 1 /* pcabi_reads_write_bam_tags tag_flags */
+typedef struct pcabi_moves_read {
+    int64_t mv_off; /* the array's first value (the stride) in the tag blob */
+    int64_t part0;  /* its parts in the part table                          */
+    int32_t l_seq;
+    int32_t n_vals; /* values of the array, the stride included             */
+    int32_t ts;     /* < 0: no ts tag                                       */
+    int32_t n_parts;
+    int32_t flags;  /* PCABI_MOVES_*                                        */
+} pcabi_moves_read;
+typedef struct pcabi_moves_part {
+    int64_t out; /* where the tag bytes go                  */
+    int32_t read;
+    int32_t s0, ns;
+    int32_t len; /* the tag bytes' length (pcabi_moves_plan) */
+} pcabi_moves_part;
+int pcabi_moves_plan(int device, const uint8_t *tags, int64_t tags_n, const pcabi_moves_read *reads, int64_t n_reads,
+                     pcabi_moves_part *parts, int64_t n_parts, uint8_t *usable);
+int pcabi_moves_remap(int device, const uint8_t *tags, int64_t tags_n, const pcabi_moves_read *reads, int64_t n_reads,
+                      const pcabi_moves_part *parts, int64_t n_parts, uint8_t *out, int64_t out_cap);
+void pcabi_moves_counts(int reset, int64_t *remapped, int64_t *dropped);
+void pcabi_moves_last_times(int reset, double *ms, int64_t *bytes);
+int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
+                               const int32_t *end_trim, const int64_t *cut_off, const int64_t *cuts,
+                               int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
+                               const char *header_text, int64_t header_len, int keep_aux, int tag_flags, int device);
 
 #ifdef __cplusplus
 }
