@@ -1500,6 +1500,8 @@ PCABI_HD Result align_lane_packed(ReadFn &rd, int n, const TabFn &tabfn, int L, 
 // stored keys are taken back to LayT keys, and LanePacked<.., LayT>'s last column and finish()
 // run unchanged (their table rows are the frame's substitution keys less a constant, ShiftRow).
 // Same scores and the same winner in every max as LayT, so the results are identical.
+// align_lane_shift4<RPL> is the same core for waves whose windows all have one length: four inner
+// columns per pass over the tile layout's dwords.
 // ==========================================================================================
 namespace pk {
 // The diagonal step into slot s, added to G of slot s - 1 at the previous column (S + OPEN, tag
@@ -1536,22 +1538,26 @@ struct LaneShift {
     int32_t k_rb;    // a rebase's score part: sc(ge P)
     int jj, P;
 
-    PCABI_HD void init(int L, const Scoring &sc, int P_, int B) {
+    // j0: column 0's phase. 0: column j runs at phase j mod P, a rebase before every column P k.
+    // -1 (column 0 stored as a rebase leaves the keys, a phase shift_range covers): column j runs
+    // at phase (j - 1) mod P and the rebases fall before the columns P k + 1 -- the boundaries of
+    // the four-column passes (align_lane_shift4) when P is a multiple of 4.
+    PCABI_HD void init(int L, const Scoring &sc, int P_, int B, int j0 = 0) {
         using pk::addw;
         const int off = RPL - L;
         P = P_;
-        jj = 0;
+        jj = j0;
         k_e = Y::sc(-sc.ge);
         k_eR = Y::sc(-sc.ge * RPL);
         k_rb = Y::sc(sc.ge * P);
-        ftop = Y::sc(-B);
-        kgo = Y::sc(sc.go - sc.ge) + ((P - 1) << Y::TB_SH);
-        int32_t fs = addw(ftop, kgo);              // sc(f(s, 0) + OPEN), tag A(0)
+        ftop = Y::sc(-sc.ge * j0 - B);
+        kgo = Y::sc(sc.go - sc.ge) + ((P - 1 - j0) << Y::TB_SH);
+        int32_t fs = addw(ftop, kgo);              // sc(f(s, j0) + OPEN), tag A(j0)
 #pragma unroll
         for (int s = 1; s <= RPL; ++s) {
             fs = addw(fs, k_e);
             st.G[s] = addw(Y::start(off - s), fs);   // S(s, 0) = 0; padded (s, 0) reaches real (0, off - s)
-            // H(s, 0) = neg_score, tag A(0) + 1 (a run just opened: to_layt() gives LayT's column-0
+            // H(s, 0) = neg_score, tag A(j0) + 1 (a run just opened: to_layt() gives LayT's column-0
             // key back when the window has one column): it loses to G in column 1
             st.HK[s] = addw(fs, Y::sc(-1) + Y::TAG1);
         }
@@ -1559,12 +1565,17 @@ struct LaneShift {
         st.bj = 0;
     }
 
+    // next column's phase, one column on, where no rebase can be due (inside a four-column pass)
+    PCABI_HD void step() {
+        ++jj;
+        kgo -= Y::TAG1;
+        ftop = pk::addw(ftop, k_e);
+    }
+
     // next column's phase: one column on, a rebase every P columns (uniform branch)
     PCABI_HD void advance() {
         using pk::addw;
-        ++jj;
-        kgo -= Y::TAG1;
-        ftop = addw(ftop, k_e);
+        step();
         if (jj == P) {
             const int32_t rb = addw(k_rb, P << Y::TB_SH);
 #pragma unroll
@@ -1621,7 +1632,8 @@ struct LaneShift {
         // row-L scout (LanePacked::column_tail): V tags are > 0, the S key's tag is cleared; the
         // corrected key goes back to LayT's frame (score less f(RPL, jj); the tag only tells V from S)
         const int32_t corr = addw(std::max(lv, ls & ~Y::TAGM), pk::negw(addw(ftop, k_eR)));
-        const bool upd = corr > (st.bkey | ((1 << Y::SC_SH) - 1));
+        // strict '>' on the scores alone: the keys' top bytes, signed (one byte-select compare)
+        const bool upd = Y::score(corr) > Y::score(st.bkey);
         st.bkey = upd ? corr : st.bkey;
         st.bj = upd ? j : st.bj;
     }
@@ -1644,9 +1656,31 @@ struct LaneShift {
     }
 };
 
+// After the inner columns: the stored keys back in LayT's frame, then LayT's last column (its table
+// row tab is the frame's, read less a constant) and finish().
+template <int RPL, int PD, typename TabRow>
+PCABI_HD Result shift_last(LaneShift<RPL, PD> &ls, const TabRow &tab, int n, int L, const Scoring &sc) {
+    using Y = pk::LayS<RPL>;
+    ls.to_layt(sc);
+    auto &st = ls.st;
+    const int32_t neg = Y::sc(pk::neg_score(sc));
+    st.k_ge = vreg(Y::sc(sc.ge));
+    st.k_go = vreg(Y::sc(sc.go));
+    st.k_gev = st.k_geh = 0;
+    st.k_gex = vreg(Y::sc(sc.ge) + Y::TB1);
+    st.k_vo = Y::TB2;
+    st.neg2 = neg | Y::TB2;
+    st.materialize(L);
+    const pk::ShiftRow<TabRow> row{tab, Y::sc(sc.ge) + ((127 - Y::TDS) << Y::TB_SH)};
+    st.template column<decltype(row), true>(row, n, L, RPL - L);
+    Best b;
+    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
+    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
+    return finish(b, L, n);
+}
+
 template <int RPL, int PD = PCABI_TAB_PD, typename ReadFn, typename TabFn>
 PCABI_HD Result align_lane_shift(ReadFn &rd, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
-    using Y = pk::LayS<RPL>;
     LaneShift<RPL, PD> ls;
     const int off = RPL - L;
     ls.init(L, sc, P, B);
@@ -1658,22 +1692,46 @@ PCABI_HD Result align_lane_shift(ReadFn &rd, int n, const TabFn &tabfn, int L, c
         ls.template column<decltype(tabfn(r))>(tabfn(r), j, off);
         r = rn;
     }
-    ls.to_layt(sc);
-    auto &st = ls.st;
-    const int32_t neg = Y::sc(pk::neg_score(sc));
-    st.k_ge = vreg(Y::sc(sc.ge));
-    st.k_go = vreg(Y::sc(sc.go));
-    st.k_gev = st.k_geh = 0;
-    st.k_gex = vreg(Y::sc(sc.ge) + Y::TB1);
-    st.k_vo = Y::TB2;
-    st.neg2 = neg | Y::TB2;
-    st.materialize(L);
-    const pk::ShiftRow<decltype(tabfn(r))> row{tabfn(r), Y::sc(sc.ge) + ((127 - Y::TDS) << Y::TB_SH)};
-    st.template column<decltype(row), true>(row, n, L, off);
-    Best b;
-    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
-    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
-    return finish(b, L, n);
+    return shift_last<RPL, PD>(ls, tabfn(r), n, L, sc);
+}
+
+// The same core for a wave whose windows all hold n columns (k_align's cross mode, run_lane): the
+// inner columns run four to a pass, a pass being one dword of the window's tile layout -- tr(q)
+// returns codes 4 q .. 4 q + 3, columns 4 q + 1 .. 4 q + 4 -- so a column's code is a constant-offset
+// byte of a word the pass already holds, and n, j and the phase stay scalars. Column 0 is stored at
+// phase -1 (LaneShift::init), so a rebase is only ever due before a pass's first column; P % 4 == 0
+// (the caller checks). The whole passes come first: the 0 .. 3 inner columns after the last whole
+// pass (all of them when n < 5) and the last column take their codes from the next dword, one
+// column() call each. Same keys per (slot, phase) and the same maxes as align_lane_shift, so the
+// results are identical; reads tr(0) .. tr((n - 1) / 4 + 1), as the window reader does.
+template <int RPL, int PD = PCABI_TAB_PD, typename TileFn, typename TabFn>
+PCABI_HD Result align_lane_shift4(const TileFn &tr, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
+    LaneShift<RPL, PD> ls;
+    const int off = RPL - L;
+    ls.init(L, sc, P, B, -1);
+    const int np = (n - 1) / 4;
+    uint32_t cur = tr(0), nx = tr(1);
+    int j = 1;
+#pragma unroll 1
+    for (int q = 0; q < np; ++q, j += 4) {
+        const uint32_t w = cur;
+        cur = nx;
+        nx = tr(q + 2);
+        ls.advance();
+        ls.template column<decltype(tabfn(0))>(tabfn((int)(w & 0xFFu)), j, off);
+        ls.step();
+        ls.template column<decltype(tabfn(0))>(tabfn((int)((w >> 8) & 0xFFu)), j + 1, off);
+        ls.step();
+        ls.template column<decltype(tabfn(0))>(tabfn((int)((w >> 16) & 0xFFu)), j + 2, off);
+        ls.step();
+        ls.template column<decltype(tabfn(0))>(tabfn((int)(w >> 24)), j + 3, off);
+    }
+#pragma unroll 1
+    for (; j < n; ++j) {
+        ls.advance();
+        ls.template column<decltype(tabfn(0))>(tabfn((int)((cur >> (8 * ((j - 1) & 3))) & 0xFFu)), j, off);
+    }
+    return shift_last<RPL, PD>(ls, tabfn((int)((cur >> (8 * ((n - 1) & 3))) & 0xFFu)), n, L, sc);
 }
 
 // Long buckets: pass 0 (c, nD) and pass 1 (m) over the same window (two readers, two tables);

@@ -213,6 +213,11 @@ __device__ __forceinline__ void fill_wave_tab_long(const KParams &p, int a_local
     __syncthreads();
 }
 
+// The gap-extend frame's four-column passes (pcabi_dp.h align_lane_shift4) run in the buckets of up
+// to 24 rows: with the 28- and 32-row instances' passes k_align_group<0> no longer fits the 96 VGPRs
+// of 5 waves per SIMD without scratch, so those keep the column-by-column loop.
+constexpr int kShift4MaxRows = 24;
+
 template <int RPL, bool AFFINE, int KIND>
 __device__ __forceinline__ void run_lane(const KParams &p, int a_local, int64_t w, int64_t out_idx,
                                          int32_t *wave_tab, int64_t tile_off) {
@@ -226,7 +231,24 @@ __device__ __forceinline__ void run_lane(const KParams &p, int a_local, int64_t 
     if (w < 0) return;
     const int n = p.win_len[w];
     pcabi::Result r;
-    if (n <= 0) {
+    bool uniform = false;
+    if constexpr (KIND == SHIFT) {
+        // Cross mode, every live lane's window of one length (a scalar n0 > 0) and a period the
+        // passes divide: the four-column passes over the tile's dwords (align_lane_shift4). The idle
+        // lanes (w < 0) have returned. Any other wave takes the column-by-column loop below.
+        const int n0 = __builtin_amdgcn_readfirstlane(n);
+        const int P = __builtin_amdgcn_readfirstlane(p.shift_p);
+        if (RPL <= kShift4MaxRows && n0 > 0 && (P & 3) == 0 && __builtin_amdgcn_ballot_w64(n != n0 || tile_off < 0) == 0) {
+            const uint32_t *base = p.tiles + tile_off + (threadIdx.x & 255);
+            auto tr = [&](int q) { return base[(int64_t)q * 256]; };
+            auto tabfn = [&](int rc) { return LdsRow{wave_tab + rc * RPL}; };
+            r = pcabi::align_lane_shift4<RPL>(tr, n0, tabfn, L, p.sc, P, p.shift_b);
+            uniform = true;
+        }
+    }
+    if (uniform) {
+        // r is the passes' result
+    } else if (n <= 0) {
         r = empty_result();
     } else {
         WindowReader rd = tile_off >= 0

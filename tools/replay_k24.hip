@@ -26,7 +26,8 @@
 // 2048 iterations -- the sustained issue rate of that instruction alone.
 //
 //   python tools/make_replay_k24.py && hipcc --offload-arch=gfx950 -O3 -o tools/replay_k24 tools/replay_k24.hip
-//   tools/replay_k24 [reps=20]     (one JSON line per measurement)
+//   tools/replay_k24 [reps=20] [first_probe=0]   (one JSON line per measurement; reps 0: the rate
+//                                                  probes only, from first_probe on)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -166,12 +167,16 @@ RP_KERNEL(k_vgconst, VGCONST, "v_mov_b32 v72, s16\n v_mov_b32 v73, s28\n", PAD0,
 #define I_BFE(i) "v_bfe_u32 %" #i ", %8, %" #i ", 4\n"
 #define I_CMPS(i) "v_cmp_gt_i32 %11, %" #i ", %8\n"
 #define I_XORMIN(i) "v_xor_b32 %" #i ", %" #i ", %8\n v_min_u32 %" #i ", 1, %" #i "\n"
+#define I_MAD24(i) "v_mad_u32_u24 %" #i ", %" #i ", %8, %9\n"
+#define I_CMPSDWA(i) "v_cmp_gt_i32_sdwa vcc, sext(%" #i "), sext(%8) src0_sel:BYTE_3 src1_sel:BYTE_3\n"
+#define I_SHR64(i) "v_lshrrev_b64 %" #i ", %8, %" #i "\n"
 
 template <int OP>
 __global__ __launch_bounds__(256) void k_rate(int *out, int seed, int iters, unsigned long long *clk) {
     const unsigned long long m64 = __builtin_amdgcn_read_exec() & 0x5555555555555555ull;
     int a0 = threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
     int b = seed, c = ~seed;
+    long long q0 = a0, q1 = a1, q2 = a2, q3 = a3, q4 = a4, q5 = a5, q6 = a6, q7 = a7;   // 64-bit chains (op 21)
     const int sg = __builtin_amdgcn_readfirstlane(seed * 3);
     const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     if (OP == 8) asm volatile("v_cmp_gt_i32 vcc, %0, %1\n" ::"v"(b), "v"(c) : "vcc");
@@ -198,6 +203,10 @@ __global__ __launch_bounds__(256) void k_rate(int *out, int seed, int iters, uns
         RATE_CASE(16, I_CND64)
         RATE_CASE(17, I_BFE)
         RATE_CASE(18, I_XORMIN)
+        RATE_CASE(19, I_MAD24)
+        RATE_CASE(20, I_CMPSDWA)
+        if (OP == 21) asm volatile(P8(I_SHR64) P8(I_SHR64) : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5),
+                                   "+v"(q6), "+v"(q7) : "v"(b));
     }
     const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if ((threadIdx.x & 63) == 0) {
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(256) void k_rate(int *out, int seed, int iters, uns
         clk[2 * w] = t1 - t0;
         clk[2 * w + 1] = r1 - r0;
     }
-    out[blockIdx.x * 256 + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
+    out[blockIdx.x * 256 + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (int)(q0 + q1 + q2 + q3 + q4 + q5 + q6 + q7);
 }
 
 using ReplayFn = void (*)(const uint32_t *, int, int, unsigned long long *);
@@ -276,6 +285,7 @@ int main(int argc, char **argv) {
     for (int w : {3, 4, 5, 6}) runs.push_back({0, w});
     runs.push_back({10, 5});
     for (const Run &r : runs) {
+        if (reps <= 0) break;   // probes only
         const Variant &v = vs[r.v];
         const int lds = lds_for(r.waves);
         auto launch = [&]() { hipLaunchKernelGGL(v.fn, dim3(blocks), dim3(256), lds, 0, d, n_tiles, n, d_clk); };
@@ -317,13 +327,14 @@ int main(int argc, char **argv) {
                            "v_max_u32", "v_max_i16", "v_pk_max_i16", "v_cndmask_b32", "v_add3_u32",
                            "v_med3_i32", "v_subrev_u32", "v_min_i32", "v_max_f32", "tagged cell (6 full + 3 max)",
                            "v_cmp_eq + v_cndmask (vcc) pair", "v_cndmask_b32_e64 (sgpr-pair mask)", "v_bfe_u32",
-                           "v_xor + v_min_u32 pair"};
+                           "v_xor + v_min_u32 pair", "v_mad_u32_u24", "v_cmp_gt_i32_sdwa (byte 3, sext)", "v_lshrrev_b64"};
     void (*rk[])(int *, int, int, unsigned long long *) = {k_rate<0>, k_rate<1>, k_rate<2>, k_rate<3>, k_rate<4>,
                                                             k_rate<5>, k_rate<6>, k_rate<7>, k_rate<8>, k_rate<9>,
                                                             k_rate<10>, k_rate<11>, k_rate<12>, k_rate<13>,
                                                             k_rate<14>, k_rate<15>, k_rate<16>, k_rate<17>,
-                                                            k_rate<18>};
-    for (int op = 0; op < 19; ++op) {
+                                                            k_rate<18>, k_rate<19>, k_rate<20>, k_rate<21>};
+    const int op0 = argc > 2 ? std::atoi(argv[2]) : 0;   // first probe to run (reps = 0 and op0 = 17: the r08 probes only)
+    for (int op = op0; op < 22; ++op) {
         // wave-instructions per asm statement (8 chains x 2 copies x instructions per chain step)
         const int per_iter = op == 14 ? 9 * 16 : ((op == 15 || op == 18) ? 2 * 16 : 16);
         auto launch = [&]() { hipLaunchKernelGGL(rk[op], dim3(rblocks), dim3(256), 0, 0, d_out, 3, iters, d_rclk); };
