@@ -142,6 +142,10 @@ def lib():
         'pcabi_gunzip_host': ([c_int, c_p, c_i64, c_p, c_i64], c_i64),
         'pcabi_gunzip_tune': ([c_i64], c_int),
         'pcabi_gunzip_last_times': ([c_p, c_p, c_p], None),
+        'pcabi_gunzip_stream_host': ([c_int, c_p, c_i64, c_p, c_i64], c_i64),
+        'pcabi_gunzip_stream_tune': ([c_i64, c_i64, c_i64], c_int),
+        'pcabi_gunzip_stream_last_stats': ([c_p], None),
+        'pcabi_gunzip_stream_last_times': ([c_int, c_int, c_p], None),
         'pcabi_bam_index': ([c_p, c_i64, c_p, c_i64, c_p], c_i64),
         'pcabi_bam_unpack_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
         'pcabi_bam_unpack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64], c_int),
@@ -211,7 +215,9 @@ def exported_symbols():
             'pcabi_bam_pack_dev', 'pcabi_bam_pack_host', 'pcabi_bam_pack_last_times', 'pcabi_reads_write_bam',
             'pcabi_fastx_keep_aux', 'pcabi_reads_aux', 'pcabi_fastx_bam_header', 'pcabi_mods_plan', 'pcabi_mods_remap',
             'pcabi_mods_counts', 'pcabi_mods_last_times', 'pcabi_moves_plan', 'pcabi_moves_remap', 'pcabi_moves_counts',
-            'pcabi_moves_last_times', 'pcabi_reads_write_bam_tags']
+            'pcabi_moves_last_times', 'pcabi_reads_write_bam_tags', 'pcabi_gunzip_stream_host',
+            'pcabi_gunzip_stream_tune', 'pcabi_gunzip_stream_last_stats', 'pcabi_gunzip_stream_last_times',
+            'pcabi_fastx_open_dev2']
 
 
 class CrossRegion(ctypes.Structure):

@@ -162,6 +162,13 @@ int gunzip_reader_device(const GunzipReader *g);
 int64_t gunzip_reader_total(const GunzipReader *g);
 void gunzip_reader_close(GunzipReader *g);
 
+// ---- pcabi_gzstream.hip --------------------------------------------------------------------------
+// the device source of a gzip input without an index (z stays mapped until close)
+struct GzStreamReader;
+int gzstream_reader_open(const uint8_t *z, int64_t n, int device, GzStreamReader **out);
+int64_t gzstream_reader_read(GzStreamReader *g, char *dst, int64_t room);
+void gzstream_reader_close(GzStreamReader *g);
+
 // ---- pcabi_bam.hip -------------------------------------------------------------------------------
 // device-event spans of the BAM timing tool: no-ops unless profiling is on
 bool prof_on();

@@ -11,7 +11,11 @@
 //   Par   lane() / lanes() / sync(): table construction strides its loops by lanes(); one lane does
 //         the serial bookkeeping; sync() separates the phases (a no-op on the host);
 //   Sink  put(pos, byte) / copy(pos, dist, len) / store(pos, src, len) / crc(len): where decoded
-//         bytes go. Every lane runs the symbol loop on the same (uniform) values.
+//         bytes go. Every lane runs the symbol loop on the same (uniform) values. A sink may say
+//         with history() how much lies before its position 0 (0 or 32768; none when it has no such
+//         member): the sinks of a decoder that starts inside a stream (pcabi_gzstream.h).
+// The block loop (inflate_blocks) starts at any bit, stops at a block boundary a stop rule picks and
+// reports where it stopped; inflate_raw is that loop from bit 0 to the final block.
 // Decode tables: a primary lookup (10 bits literal/length, 9 bits distance, 7 bits code lengths)
 // whose entries for longer codes point at second-level tables of 2^(longest code below - root)
 // entries. The sizes below always suffice: a second-level table of 2^k entries is full (incomplete
@@ -293,16 +297,49 @@ PCABI_HD PCABI_INL inline void fixed_lengths(Par &par, Tables &t) {
     par.sync();
 }
 
-// The deflate stream in [z, z + n) into the sink, at most limit bytes. *produced = bytes decoded,
-// *used = input bytes consumed (whole bytes: the final block's padding counts). Every loop below
-// drops at least one input bit per turn or returns.
-template <class Par, class Sink>
-PCABI_HD PCABI_INL inline int inflate_raw(Par &par, Sink &sink, Tables &t, const uint8_t *z, int64_t n, uint32_t limit,
-                                uint32_t *produced, int64_t *used) {
-    Bits b{z, (uint32_t)n, 0, 0, 0};
+// How much history lies before a sink's position 0: what its history() says (0, or 32768 for a sink
+// that stands for an unknown window), 0 for a sink without one.
+template <class Sink>
+PCABI_HD PCABI_INL inline auto sink_history(const Sink &s, int) -> decltype((uint32_t)s.history()) {
+    return (uint32_t)s.history();
+}
+template <class Sink>
+PCABI_HD PCABI_INL inline uint32_t sink_history(const Sink &, long) {
+    return 0;
+}
+
+// the stop rule of a decoder that runs to the final block
+struct NeverStop {
+    PCABI_HD bool operator()(int64_t) const { return false; }
+};
+
+// a bit reader over [z, z + n) that stands on bit `bit` (0 <= bit <= 8 n)
+PCABI_HD PCABI_INL inline Bits bits_at(const uint8_t *z, uint32_t n, int64_t bit) {
+    Bits b{z, n, (uint32_t)(bit >> 3), 0, 0};
+    const int k = (int)(bit & 7);
+    if (k && b.pos < n) {
+        b.buf = (uint64_t)(z[b.pos++] >> k);
+        b.cnt = 8 - k;
+    }
+    return b;
+}
+// the bit the reader stands on
+PCABI_HD PCABI_INL inline int64_t bit_pos(const Bits &b) { return 8 * (int64_t)b.pos - b.cnt; }
+
+// Deflate blocks from the bit b stands on into the sink, at most limit bytes, until a final block
+// has been decoded or stop(bit position) holds at a block boundary (asked after every block that is
+// not final). *produced = bytes decoded, *end_bit = the bit after the last block decoded,
+// *was_final = that block was a final one. A match may reach sink_history() bytes before the
+// sink's position 0. Every loop below drops at least one input bit per turn or returns.
+template <class Par, class Sink, class Stop>
+PCABI_HD PCABI_INL inline int inflate_blocks(Par &par, Sink &sink, Tables &t, Bits &b, uint32_t limit, const Stop &stop,
+                                   uint32_t *produced, int64_t *end_bit, int *was_final) {
+    const uint8_t *z = b.p;
+    const uint32_t hist = sink_history(sink, 0);
     uint32_t opos = 0;
     *produced = 0;
-    *used = 0;
+    *end_bit = 0;
+    *was_final = 0;
     if (par.lane() == 0) t.fixed_built = 0;
     par.sync();
     for (;;) {
@@ -363,15 +400,36 @@ PCABI_HD PCABI_INL inline int inflate_raw(Par &par, Sink &sink, Tables &t, const
                 if (e_type(d) != T_DIST) return PCABI_INFLATE_E_CODE;
                 if (!take(b, (int)e_extra(d), &x)) return PCABI_INFLATE_E_INPUT;
                 const uint32_t dist = e_val(d) + x;
-                if (dist > opos) return PCABI_INFLATE_E_DIST;
+                if (dist > opos && dist - opos > hist) return PCABI_INFLATE_E_DIST;
                 if (len > limit - opos) return PCABI_INFLATE_E_OUTPUT;
                 sink.copy(opos, dist, len);
                 opos += len;
             }
         }
-        if (final_block) break;
+        if (final_block) {
+            *was_final = 1;
+            break;
+        }
+        if (stop(bit_pos(b))) break;
     }
     *produced = opos;
+    *end_bit = bit_pos(b);
+    return 0;
+}
+
+// The deflate stream in [z, z + n) into the sink, at most limit bytes. *produced = bytes decoded,
+// *used = input bytes consumed (whole bytes: the final block's padding counts).
+template <class Par, class Sink>
+PCABI_HD PCABI_INL inline int inflate_raw(Par &par, Sink &sink, Tables &t, const uint8_t *z, int64_t n, uint32_t limit,
+                                uint32_t *produced, int64_t *used) {
+    Bits b{z, (uint32_t)n, 0, 0, 0};
+    int64_t end_bit = 0;
+    int was_final = 0;
+    *used = 0;
+    if (int rc = inflate_blocks(par, sink, t, b, limit, NeverStop(), produced, &end_bit, &was_final)) {
+        *produced = 0;
+        return rc;
+    }
     *used = (int64_t)(b.pos - (uint32_t)(b.cnt >> 3));
     return 0;
 }
@@ -472,6 +530,55 @@ struct SerialPar {
     PCABI_HD int lane() const { return 0; }
     PCABI_HD int lanes() const { return 1; }
     PCABI_HD void sync() const {}
+};
+
+// ---- sinks of a decoder that starts inside a stream (pcabi_gzstream.h) --------------------------
+// Symbols instead of bytes: a value below 256 is a byte; kMarker | j stands for byte j of the 32768
+// bytes that precede the sink's position 0 (the window of whatever was decoded before, unknown
+// while this decoder runs). ring holds the last 32768 symbols and is the LZ77 window, out (when not
+// null) receives every symbol; matches copy symbols, so markers travel with them.
+constexpr uint32_t kWindow = 32768;
+constexpr uint16_t kMarker = 0x8000;
+
+// ring[j] = the symbol at position j - 32768: the unknown window, as markers
+template <class Par>
+PCABI_HD PCABI_INL inline void marker_ring_init(Par &par, uint16_t *ring) {
+    for (uint32_t j = (uint32_t)par.lane(); j < kWindow; j += (uint32_t)par.lanes()) ring[j] = (uint16_t)(kMarker | j);
+    par.sync();
+}
+
+struct SerialMarkerSink {
+    uint16_t *ring;   // kWindow symbols
+    uint16_t *out;
+    uint32_t hist;    // 0: nothing precedes position 0 (a member's start); kWindow: markers do
+    PCABI_HD uint32_t history() const { return hist; }
+    PCABI_HD void put(uint32_t pos, uint8_t c) {
+        ring[pos & (kWindow - 1)] = c;
+        out[pos] = c;
+    }
+    // a source may be written by this very copy (dist < len): ascending order reads it after
+    PCABI_HD void copy(uint32_t pos, uint32_t dist, uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i) {
+            const uint16_t s = ring[(pos + i - dist) & (kWindow - 1)];
+            ring[(pos + i) & (kWindow - 1)] = s;
+            out[pos + i] = s;
+        }
+    }
+    PCABI_HD void store(uint32_t pos, const uint8_t *src, uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i) {
+            ring[(pos + i) & (kWindow - 1)] = src[i];
+            out[pos + i] = src[i];
+        }
+    }
+};
+
+// sizes only: a decoder over this sink writes nothing
+struct CountSink {
+    uint32_t hist;
+    PCABI_HD uint32_t history() const { return hist; }
+    PCABI_HD void put(uint32_t, uint8_t) const {}
+    PCABI_HD void copy(uint32_t, uint32_t, uint32_t) const {}
+    PCABI_HD void store(uint32_t, const uint8_t *, uint32_t) const {}
 };
 
 #if !defined(__HIPCC__)

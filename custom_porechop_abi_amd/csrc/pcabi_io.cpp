@@ -110,7 +110,8 @@ struct BamState {
 struct pcabi_fastx {
     gzFile f = nullptr;
     pcabi_internal::GunzipReader *dev = nullptr;   // block-gzipped input inflated on the device, instead of f
-    void *zmap = nullptr;                          // its compressed bytes, mapped whole
+    pcabi_internal::GzStreamReader *zs = nullptr;  // gzip without an index inflated on the device, instead of f
+    void *zmap = nullptr;                          // the compressed bytes of dev / zs, mapped whole
     size_t zmap_len = 0;
     int type = -1;                 // PCABI_FASTA / PCABI_FASTQ
     BamState *bam = nullptr;       // the input is a BAM file (type PCABI_FASTQ): records instead of lines
@@ -350,6 +351,11 @@ bool next_line(pcabi_fastx *r, const char **p, size_t *n) {
             got = k < 0 ? -1 : (int)k;
             bad = k < 0;
             if (bad) zmsg = pcabi_last_error();
+        } else if (r->zs) {
+            const int64_t k = pcabi_internal::gzstream_reader_read(r->zs, r->buf.data() + r->end, (int64_t)room);
+            got = k < 0 ? -1 : (int)k;
+            bad = k < 0;
+            if (bad) zmsg = pcabi_last_error();
         } else {
             got = gzread(r->f, r->buf.data() + r->end, (unsigned)room);
             int zerr = Z_OK;
@@ -577,7 +583,7 @@ int pcabi_internal::io_thread_count() { return io_threads(); }
 
 extern "C" {
 
-static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **out) {
+static int fastx_open_impl(const char *path, int raw, int device, int flags, pcabi_fastx **out) {
     if (!path || !out) return fail(PCABI_E_ARG, "bad arguments");
     *out = nullptr;
     FILE *fp = std::fopen(path, "rb");
@@ -635,7 +641,24 @@ static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **
         }
         if (fd >= 0) ::close(fd);
     }
-    if (!r->map && !r->dev) {
+    if (gz && device >= 0 && !r->dev && (flags & PCABI_OPEN_GUNZIP_PLAIN)) {
+        // gzip without an index: map the compressed file, inflate span by span on the device
+        const int fd = ::open(path, O_RDONLY);
+        struct stat st;
+        if (fd >= 0 && fstat(fd, &st) == 0 && st.st_size > 0) {
+            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) {
+                if (pcabi_internal::gzstream_reader_open((const uint8_t *)m, (int64_t)st.st_size, device, &r->zs) == 0 && r->zs) {
+                    r->zmap = m;
+                    r->zmap_len = (size_t)st.st_size;
+                } else {
+                    munmap(m, (size_t)st.st_size);
+                }
+            }
+        }
+        if (fd >= 0) ::close(fd);
+    }
+    if (!r->map && !r->dev && !r->zs) {
         gzFile f = gzopen(path, "rb");
         if (!f) {
             delete r;
@@ -655,8 +678,14 @@ static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **
         r->base = r->buf.data();
         // type from the first decoded character
         while (r->end == 0 && !r->eof) {
-            const int64_t got = r->dev ? pcabi_internal::gunzip_reader_read(r->dev, r->buf.data(), (int64_t)r->buf.size())
-                                       : (int64_t)gzread(r->f, r->buf.data(), (unsigned)r->buf.size());
+            const int64_t got = r->dev  ? pcabi_internal::gunzip_reader_read(r->dev, r->buf.data(), (int64_t)r->buf.size())
+                                : r->zs ? pcabi_internal::gzstream_reader_read(r->zs, r->buf.data(), (int64_t)r->buf.size())
+                                        : (int64_t)gzread(r->f, r->buf.data(), (unsigned)r->buf.size());
+            if (got < 0 && r->zs && r->end == 0) {
+                // nothing decodes: the zlib reader finds no type either ("neither FASTA or FASTQ")
+                r->eof = true;
+                break;
+            }
             if (got < 0 && r->dev) {   // a member that does not inflate, or a device error: not "no type"
                 pcabi_fastx_close(r);
                 return (int)got;
@@ -666,6 +695,11 @@ static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **
         }
     }
     const char c0 = r->end ? r->base[0] : 0;
+    if (r->zs && r->end >= 4 && std::memcmp(r->base, "BAM", 3) == 0) {
+        // a BAM file that is not block-gzipped: its records are read through zlib
+        pcabi_fastx_close(r);
+        return fastx_open_impl(path, raw, device, flags & ~PCABI_OPEN_GUNZIP_PLAIN, out);
+    }
     if (!r->map && r->end >= 4 && std::memcmp(r->base, "BAM", 3) == 0) {
         // unaligned BAM: the version byte is checked with the header (a read error of the first batch)
         r->type = PCABI_FASTQ;
@@ -695,10 +729,15 @@ static int fastx_open_impl(const char *path, int raw, int device, pcabi_fastx **
     return 0;
 }
 
-int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) { return fastx_open_impl(path, raw, -1, out); }
+int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out) { return fastx_open_impl(path, raw, -1, 0, out); }
 
 int pcabi_fastx_open_dev(const char *path, int raw, int device, pcabi_fastx **out) {
-    return fastx_open_impl(path, raw, device, out);
+    return fastx_open_impl(path, raw, device, 0, out);
+}
+
+int pcabi_fastx_open_dev2(const char *path, int raw, int device, int flags, pcabi_fastx **out) {
+    if (flags & ~PCABI_OPEN_GUNZIP_PLAIN) return fail(PCABI_E_ARG, "unknown open flags");
+    return fastx_open_impl(path, raw, device, flags, out);
 }
 
 int pcabi_fastx_type(const pcabi_fastx *r) { return r ? r->type : -1; }
@@ -790,6 +829,7 @@ void pcabi_fastx_close(pcabi_fastx *r) {
         delete r->bam;
     }
     if (r->dev) pcabi_internal::gunzip_reader_close(r->dev);
+    if (r->zs) pcabi_internal::gzstream_reader_close(r->zs);
     if (r->zmap) munmap(r->zmap, r->zmap_len);
     r->ahead_stop = true;                 // the populate-ahead helper leaves the mapping first
     if (r->ahead.joinable()) r->ahead.join();

@@ -746,6 +746,41 @@ def gunzip(data, device=0, cap=None):
     return out[:n].tobytes()
 
 
+# ---- gunzip on the device, streams without an index (csrc/pcabi_gzstream.hip) ----------------------
+GUNZIP_STREAM_STATS = ('spans', 'cuts', 'confirmed', 'rejected', 'members', 'dev_bytes', 'host_bytes')
+
+
+def gunzip_stream(data, device=0, cap=None):
+    """Any gzip stream (ordinary gzip, multi-member gzip, BGZF) inflated on GPU `device`
+    (pcabi_gunzip_stream_host): chunks of the deflate stream decoded in parallel from speculative block
+    starts, spans the device cannot take through zlib. Returns bytes, zlib's exactly; a bad stream
+    raises PcabiError naming the member, its offset and the status. cap (tests): the output capacity
+    offered; a too small one raises ValueError naming the size needed."""
+    buf, _ = _gzip_input(data, None)
+    L = lib()
+    size = max(4 * buf.size, 1 << 16) if cap is None else int(cap)
+    while True:
+        out = np.empty(max(size, 1), np.uint8)
+        n = L.pcabi_gunzip_stream_host(int(device), _ptr(buf), buf.size, _ptr(out), size)
+        if n < 0:
+            check(int(n), 'pcabi_gunzip_stream_host')
+        if n <= size:
+            return out[:n].tobytes()
+        if cap is not None:
+            raise ValueError('gunzip_stream: capacity %d, needed %d' % (size, n))
+        size = int(n)
+
+
+def gunzip_stream_stats():
+    """What the last gunzip_stream call, or the reader last read from (misc.read_batches gunzip_plain),
+    did on this thread (pcabi_gunzip_stream_last_stats): a dict of spans, chunk cuts, chunks confirmed on
+    the chain, rejected candidates, members, bytes decoded on the device, bytes decoded by the host
+    fallback."""
+    s = np.zeros(len(GUNZIP_STREAM_STATS), np.int64)
+    lib().pcabi_gunzip_stream_last_stats(_ptr(s))
+    return dict(zip(GUNZIP_STREAM_STATS, (int(x) for x in s)))
+
+
 # ---- unaligned BAM input (csrc/pcabi_bam.h, csrc/pcabi_bam.hip) ----------------------------------
 # include/pcabi.h pcabi_bam_rec
 BAM_REC = np.dtype([('rec', np.int64), ('seq_out', np.int64), ('qual_out', np.int64), ('code_out', np.int64),

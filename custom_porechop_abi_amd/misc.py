@@ -39,6 +39,7 @@ def _declare(L):
     sig = {
         'pcabi_fastx_open': ([ctypes.c_char_p, c_int, ctypes.POINTER(P)], c_int),
         'pcabi_fastx_open_dev': ([ctypes.c_char_p, c_int, c_int, ctypes.POINTER(P)], c_int),
+        'pcabi_fastx_open_dev2': ([ctypes.c_char_p, c_int, c_int, c_int, ctypes.POINTER(P)], c_int),
         'pcabi_fastx_type': ([P], c_int),
         'pcabi_fastx_next': ([P, i64, i64, ctypes.POINTER(P)], i64),
         'pcabi_fastx_close': ([P], None),
@@ -281,13 +282,23 @@ def is_bam(path):
         return False
 
 
-def _fastx_open(L, path, raw, gunzip_device, keep_aux=False):
+OPEN_GUNZIP_PLAIN = 1   # include/pcabi.h PCABI_OPEN_GUNZIP_PLAIN
+
+
+def _check_gunzip_plain(gunzip_device, gunzip_plain):
+    if gunzip_plain and gunzip_device is None:
+        raise ValueError('gunzip_plain needs gunzip_device')
+
+
+def _fastx_open(L, path, raw, gunzip_device, keep_aux=False, gunzip_plain=False):
     """pcabi_fastx_open, or pcabi_fastx_open_dev when gunzip_device names a GPU (a block-gzipped file
-    is then inflated there; any other file reads as before). keep_aux: pcabi_fastx_keep_aux. Returns
-    (rc, handle)."""
+    is then inflated there; any other file reads as before, unless gunzip_plain sends ordinary gzip
+    there too: pcabi_fastx_open_dev2). keep_aux: pcabi_fastx_keep_aux. Returns (rc, handle)."""
     h = ctypes.c_void_p()
     if gunzip_device is None:
         rc = L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h))
+    elif gunzip_plain:
+        rc = L.pcabi_fastx_open_dev2(os.fsencode(path), int(raw), int(gunzip_device), OPEN_GUNZIP_PLAIN, ctypes.byref(h))
     else:
         rc = L.pcabi_fastx_open_dev(os.fsencode(path), int(raw), int(gunzip_device), ctypes.byref(h))
     if rc == 0 and keep_aux:
@@ -316,7 +327,7 @@ def ramp_sizes(max_reads, remaining_reads=None, done=0):
 
 
 def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_range=None, first_reads=None,
-                 ramp=False, gunzip_device=None, keep_aux=False):
+                 ramp=False, gunzip_device=None, keep_aux=False, gunzip_plain=False):
     """Stream a FASTA / FASTQ(.gz) or unaligned BAM file as ReadBatch objects (pcabi_fastx_next; a BAM
     file's records arrive as FASTQ batches, see include/pcabi.h "unaligned BAM input"); byte_range =
     (begin, end) record starts of a plain file (record_boundaries) reads only that range;
@@ -325,11 +336,14 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
     batches shrink too, from the bytes left and the bytes per read so far). Batching never changes
     what is read or written, only when. gunzip_device: a GPU that inflates a block-gzipped (BGZF)
     input (pcabi_fastx_open_dev) and, for a BAM file, unpacks its records; None reads every gzip
-    input with zlib. keep_aux: a BAM input's batches keep their records' aux tags (ReadBatch.aux),
+    input with zlib; gunzip_plain (with gunzip_device): ordinary gzip, which has no index, is inflated
+    there too, in parallel from speculative block starts (include/pcabi.h pcabi_gunzip_stream_*).
+    keep_aux: a BAM input's batches keep their records' aux tags (ReadBatch.aux),
     for write_reads(..., 'bam', keep_aux=True); any other input: no effect. A BAM input's batches
     carry its header text (ReadBatch.bam_header)."""
+    _check_gunzip_plain(gunzip_device, gunzip_plain)
     L = _declare(lib())
-    rc, h = _fastx_open(L, path, raw, gunzip_device, keep_aux)
+    rc, h = _fastx_open(L, path, raw, gunzip_device, keep_aux, gunzip_plain)
     if rc != 0:
         raise ValueError(_open_error(path))
     if byte_range is not None and L.pcabi_fastx_set_range(h, int(byte_range[0]), int(byte_range[1])) != 0:
@@ -362,14 +376,15 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
         L.pcabi_fastx_close(h)
 
 
-def text_chunks(path, chunk_bytes, gunzip_device=None):
+def text_chunks(path, chunk_bytes, gunzip_device=None, gunzip_plain=False):
     """Stream a FASTA / FASTQ(.gz) file (not BAM: its records are binary, the reader refuses) as
     spans of its decoded text holding whole records, cut
     where a fresh reader parses the same records (pcabi_fastx_next_text): yields memoryviews of at
     least chunk_bytes (the last may be shorter), each valid until the next one is requested.
-    gunzip_device: as in read_batches."""
+    gunzip_device, gunzip_plain: as in read_batches."""
+    _check_gunzip_plain(gunzip_device, gunzip_plain)
     L = _declare(lib())
-    rc, h = _fastx_open(L, path, 0, gunzip_device)
+    rc, h = _fastx_open(L, path, 0, gunzip_device, False, gunzip_plain)
     if rc != 0:
         raise ValueError(_open_error(path))
     try:
@@ -385,15 +400,18 @@ def text_chunks(path, chunk_bytes, gunzip_device=None):
         L.pcabi_fastx_close(h)
 
 
-def load_batch(path, raw=False, gunzip_device=None, keep_aux=False):
+def load_batch(path, raw=False, gunzip_device=None, keep_aux=False, gunzip_plain=False):
     """The whole FASTA, FASTQ or BAM file as one ReadBatch (pcabi_fastx_load); raw keeps the file's
     own text. gunzip_device: a GPU that inflates a block-gzipped (BGZF) input, a BAM file included,
-    whose records are then unpacked there too (pcabi_fastx_open_dev). keep_aux: as in read_batches."""
+    whose records are then unpacked there too (pcabi_fastx_open_dev). keep_aux, gunzip_plain: as in
+    read_batches."""
+    _check_gunzip_plain(gunzip_device, gunzip_plain)
     L = _declare(lib())
     b = ctypes.c_void_p()
     bam = is_bam(path)
-    if bam or (gunzip_device is not None and _starts_bgzf(path)):
-        rc, h = _fastx_open(L, path, raw, gunzip_device if _starts_bgzf(path) else None, keep_aux)
+    plain = bool(gunzip_plain) and not bam and get_compression_type(path) == 'gz' and not _starts_bgzf(path)
+    if bam or plain or (gunzip_device is not None and _starts_bgzf(path)):
+        rc, h = _fastx_open(L, path, raw, gunzip_device if (plain or _starts_bgzf(path)) else None, keep_aux, plain)
         if rc != 0:
             raise ValueError(_open_error(path))
         try:

@@ -64,6 +64,7 @@ class FileTrimmer(object):
     gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
     bgzf = False                          # device-compressed '.gz' output as plain multi-member gzip
     gunzip_device = None                  # gzip inputs through zlib on the host (set by __init__)
+    gunzip_plain = False                  # with gunzip_device: ordinary gzip inputs on the device too
     keep_tags = False                     # BAM to BAM: aux tags are dropped (set by __init__)
     keep_mods = False                     # with keep_tags: MM ML MN of changed reads are dropped, not remapped
     keep_moves = False                    # with keep_tags: mv of changed reads is dropped, ts copied
@@ -74,7 +75,7 @@ class FileTrimmer(object):
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
-                 keep_mods=False, keep_moves=False):
+                 keep_mods=False, keep_moves=False, gunzip_plain=False):
         self.L = L = lib()
         # out_format 'bam' from a BAM input: the records' aux tags are read and written (misc.write_reads
         # keep_aux: verbatim on reads written whole and as stored, without the position-dependent tags
@@ -101,6 +102,11 @@ class FileTrimmer(object):
         # block-gzipped (BGZF) inputs: zlib on the host (default) or inflated on the device by the reader
         # thread (misc.read_batches gunzip_device); any other input reads as before
         self.gunzip_device = self.device if gunzip_on_device else None
+        # with gunzip_on_device: ordinary gzip inputs (no index) are inflated on the device as well
+        # (misc.read_batches gunzip_plain)
+        if gunzip_plain and not gunzip_on_device:
+            raise ValueError('gunzip_plain needs gunzip_on_device=True')
+        self.gunzip_plain = bool(gunzip_plain)
         check(L.pcabi_dev_set(device), 'pcabi_dev_set')
         self.sc = tuple(int(x) for x in scoring_scheme_vals[:4])
         self.E, self.thr, self.extra, self.min_trim = int(end_size), float(end_threshold), int(extra_end_trim), \
@@ -333,8 +339,13 @@ class FileTrimmer(object):
                 # parse and the last write are small, so they overlap the other stages
                 for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True,
                                            gunzip_device=getattr(self, 'gunzip_device', None),
-                                           keep_aux=out_format == 'bam' and bool(getattr(self, 'keep_tags', False))):
+                                           keep_aux=out_format == 'bam' and bool(getattr(self, 'keep_tags', False)),
+                                           gunzip_plain=bool(getattr(self, 'gunzip_plain', False))):
                     yield b, alb
+                if getattr(self, 'gunzip_plain', False):
+                    # the reader thread's own figures (engine.gunzip_stream_stats is per thread)
+                    from . import engine
+                    self.gunzip_stream_stats = engine.gunzip_stream_stats()
 
         def produce():
             try:

@@ -652,6 +652,8 @@ int pcabi_fastx_open(const char *path, int raw, pcabi_fastx **out);
  * ..."), raised after the records before it. A plain file, a gzip file that is not indexable and
  * device < 0 behave exactly as pcabi_fastx_open. The calling thread's current device may change. */
 int pcabi_fastx_open_dev(const char *path, int raw, int device, pcabi_fastx **out);
+/* with flags (PCABI_OPEN_GUNZIP_PLAIN): see "gunzip on the device, streams without an index" */
+int pcabi_fastx_open_dev2(const char *path, int raw, int device, int flags, pcabi_fastx **out);
 int pcabi_fastx_type(const pcabi_fastx *r);
 /* Byte-range reading of a plain (not gzip) file, for read shards split by position:
  *   pcabi_fastx_record_start : the first record start at or after `byte` (the file size if
@@ -817,6 +819,45 @@ int pcabi_gunzip_dev(void *stream, const uint8_t *z, int64_t n, const int64_t *i
 int64_t pcabi_gunzip_host(int device, const uint8_t *z, int64_t n, uint8_t *out, int64_t cap);
 int pcabi_gunzip_tune(int64_t chunk_bytes);
 void pcabi_gunzip_last_times(double *copy_in, double *wait, double *copy_out);
+
+/* ---- gunzip on the device, streams without an index (csrc/pcabi_gzstream.hip) ------------
+ * Ordinary gzip (what gzip, pigz and the sequencers write: one deflate stream per member, no BC
+ * subfield), opt-in. The compressed bytes are processed in spans of span_bytes, each cut at
+ * multiples of chunk_bytes: every cut looks for the first place a block may start (a non-final
+ * dynamic block header that parses, or a member header), a decoder starts there with the unknown
+ * 32768 bytes before it kept as symbolic markers and stops at the first block boundary that is
+ * another cut's candidate. The host follows the chain from the span's known start, sizes the
+ * chunks on it, and the device hands the windows down the chain, replaces the markers and computes
+ * the CRC-32 of every piece; each member's CRC-32 and ISIZE (modulo 2^32) are checked against its
+ * trailer. A span with fewer than min_chunks chunks on the chain, or whose chain breaks at its
+ * start, goes through zlib's raw inflate from the same bit with the same window. The decoded bytes
+ * are zlib's either way; trailing bytes that are no member start are ignored, as gzread does.
+ *   pcabi_gunzip_stream_host : host buffers (pageable), any gzip stream, a BGZF one included.
+ *       Returns the decoded length; the needed length, with out untouched, when cap is smaller;
+ *       PCABI_E_PARSE when the stream is bad (the message names the member's index, its byte offset
+ *       and the PCABI_INFLATE_E_* status). An empty input decodes to nothing. device -1 = current.
+ *   pcabi_gunzip_stream_tune : test switch, process-wide: compressed bytes per chunk and per span,
+ *       and the fewest chunks on a span's chain that keep it on the device (0 = the default of each:
+ *       64 KiB, 64 MiB, 1).
+ *   pcabi_gunzip_stream_last_stats : s[0..6] of the last pcabi_gunzip_stream_host call, or of the
+ *       reader last read from, on this thread: spans, chunk cuts, chunks on the chain, rejected
+ *       candidates, members, bytes decoded on the device, bytes decoded by the host fallback.
+ *   pcabi_gunzip_stream_last_times : milliseconds from device events, summed since the last call
+ *       with reset != 0: ms[0] finder, ms[1] counting pass, ms[2] decode, ms[3] window hand-down,
+ *       ms[4] resolve. Events are recorded (and every kernel waited for) only while on = 1; on = 0
+ *       turns that off; -1 leaves it.
+ *   pcabi_fastx_open_dev2 : pcabi_fastx_open_dev with flags. PCABI_OPEN_GUNZIP_PLAIN: a gzip file
+ *       that is not block-gzipped is read through this path, span by span on a stream and a thread
+ *       of the reader's own, so the next span inflates while the parser works on the current one. A
+ *       BGZF file still takes the indexed path; a BAM file that is not block-gzipped reads through
+ *       zlib. Errors are the zlib path's: the records before the bad place, then the read error.
+ * There is no entry with device pointers: following the chain and sizing the chunks need the host
+ * between the kernels. */
+enum { PCABI_OPEN_GUNZIP_PLAIN = 1 };
+int64_t pcabi_gunzip_stream_host(int device, const uint8_t *z, int64_t n, uint8_t *out, int64_t cap);
+int pcabi_gunzip_stream_tune(int64_t chunk_bytes, int64_t span_bytes, int64_t min_chunks);
+void pcabi_gunzip_stream_last_stats(int64_t *s);
+void pcabi_gunzip_stream_last_times(int on, int reset, double *ms);
 
 /* ---- unaligned BAM input (csrc/pcabi_bam.h, csrc/pcabi_bam.hip) ------------------------------
  * The reader (pcabi_fastx_open / pcabi_fastx_open_dev) takes a BAM file as a third input type: its
