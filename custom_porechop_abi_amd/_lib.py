@@ -171,6 +171,16 @@ def lib():
         'pcabi_moves_remap': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
         'pcabi_moves_counts': ([c_int, c_p, c_p], None),
         'pcabi_moves_last_times': ([c_int, c_p, c_p], None),
+        'pcabi_auxtext_plan': ([c_int, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_auxtext_write': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_auxtext_counts': ([c_int, c_p, c_p], None),
+        'pcabi_auxtext_last_times': ([c_int, c_int, c_p, c_p], None),
+        'pcabi_fastx_pack_plan': ([c_p, c_i64, c_int, c_i64, c_p], c_i64),
+        'pcabi_fastx_pack_dev': ([c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_int, c_p, c_p, c_i64, c_p, c_i64],
+                                 c_int),
+        'pcabi_fastx_pack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_p, c_i64], c_int),
+        'pcabi_reads_write_tags': ([c_p, ctypes.c_char_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_int,
+                                    c_int, c_int, c_int], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -217,7 +227,9 @@ def exported_symbols():
             'pcabi_mods_counts', 'pcabi_mods_last_times', 'pcabi_moves_plan', 'pcabi_moves_remap', 'pcabi_moves_counts',
             'pcabi_moves_last_times', 'pcabi_reads_write_bam_tags', 'pcabi_gunzip_stream_host',
             'pcabi_gunzip_stream_tune', 'pcabi_gunzip_stream_last_stats', 'pcabi_gunzip_stream_last_times',
-            'pcabi_fastx_open_dev2']
+            'pcabi_fastx_open_dev2', 'pcabi_auxtext_plan', 'pcabi_auxtext_write', 'pcabi_auxtext_counts',
+            'pcabi_auxtext_last_times', 'pcabi_fastx_pack_plan', 'pcabi_fastx_pack_dev', 'pcabi_fastx_pack_host',
+            'pcabi_reads_write_tags']
 
 
 class CrossRegion(ctypes.Structure):

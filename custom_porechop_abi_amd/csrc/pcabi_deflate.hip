@@ -704,6 +704,20 @@ int pcabi_bgzf_dev(void *stream, const uint8_t *in, int64_t n, int64_t block_len
     return launch((hipStream_t)stream, in, n, nullptr, nb, block_len, 1, 18, out, cap, out_len, scratch);
 }
 
+}  // extern "C"
+
+// pcabi_bgzf_dev with the caller's block list: the text writer's line-aligned members (pcabi_auxtext.hip)
+int pcabi_internal::bgzf_dev_blocks(void *stream, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks,
+                                    uint8_t *out, int64_t cap, int64_t *out_len, void *scratch, int64_t scratch_len) {
+    if (n < 0 || n_blocks < 0 || cap < 0 || !out_len || !scratch || !block_off || (n > 0 && !in) || (cap > 0 && !out) ||
+        (n > 0) != (n_blocks > 0) || n_blocks > INT32_MAX)
+        return fail(PCABI_E_ARG, "bad arguments");
+    if (scratch_len < scratch_bytes(n_blocks)) return fail(PCABI_E_ARG, "scratch smaller than pcabi_gzip_scratch_bytes");
+    return launch((hipStream_t)stream, in, n, block_off, n_blocks, kBgzfBlockCap, 1, 18, out, cap, out_len, scratch);
+}
+
+extern "C" {
+
 int pcabi_bgzf_write_eof(const char *path) {
     if (!path) return fail(PCABI_E_ARG, "bad arguments");
     FILE *f = std::fopen(path, "ab");

@@ -1,5 +1,5 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
 // the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
 // pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
 // compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
@@ -267,5 +267,30 @@ void moves_host_free(MovesHost *h);
 MovesDev *moves_dev_new();
 void moves_dev_free(MovesDev *d);   // its device current
 int64_t moves_host_ns(int reset, int64_t *dev_plan_ns);   // pcabi_moves_last_times
+
+// ---- pcabi_deflate.hip ---------------------------------------------------------------------------
+// pcabi_bgzf_dev with a block list (device pointer, n_blocks + 1 entries, every block 1..65280 bytes):
+// one BGZF member per block; scratch of pcabi_gzip_scratch_bytes(n, n_blocks)
+int bgzf_dev_blocks(void *stream, const uint8_t *in, int64_t n, const int64_t *block_off, int64_t n_blocks, uint8_t *out,
+                    int64_t cap, int64_t *out_len, void *scratch, int64_t scratch_len);
+
+// ---- pcabi_auxtext.hip ---------------------------------------------------------------------------
+// The device half of the text writer with tags in the headers (pcabi_reads_write_tags, gz = 2 / 3): the
+// letters go up, the remapped tags are sized as for BAM output, `layout` then builds the side blob with
+// its gaps, sets the tables' out to the gaps and fills the job (the parts without text_len / out /
+// tile0; kept[i] = the bytes of part i's chain that lie before its gaps); the gaps are filled in the
+// device copy of the blob, the chains' texts sized there, the records and the deflate blocks planned
+// on the host, the text laid out and compressed on the device; sink receives the compressed bytes
+// (pinned memory, valid inside the call). Returns their length or a negative code.
+struct FastxWriteJob {
+    const uint8_t *side = nullptr;
+    int64_t side_n = 0;
+    pcabi_fastx_part *parts = nullptr;
+    const int32_t *kept = nullptr;
+    int64_t n_parts = 0;
+};
+int64_t fastx_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables *mods,
+                             const MovesTables *moves, bool fasta, bool bgzf, const std::function<void(FastxWriteJob *)> &layout,
+                             const std::function<void(const uint8_t *, int64_t)> &sink);
 
 }  // namespace pcabi_internal

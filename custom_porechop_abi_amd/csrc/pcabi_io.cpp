@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "../../include/pcabi.h"
+#include "pcabi_auxtext.h"
 #include "pcabi_bam.h"
 #include "pcabi_deflate.h"
 #include "pcabi_hostdev.h"
@@ -1872,6 +1873,203 @@ int64_t moves_read_of(const uint8_t *aux, int64_t a0, int64_t a1, int64_t l_seq,
     return (int64_t)reads->size() - 1;
 }
 
+// What the BAM writer and the text writer with tags in its headers (pcabi_reads_write_tags) share: the
+// parts of a batch, the tables of the tags to remap, and the side blob (per part its name, then its aux
+// bytes) with a gap behind each part's kept tags for what is remapped.
+struct TagParts {
+    const pcabi_reads *b;
+    const WriteArgs &wa;
+    const bool have_aux, remap, keep_moves, no_qual;
+    const int nt;
+    // the changed reads that carry modification tags and their parts (include/pcabi.h pcabi_mods_*; the tag
+    // blob is the batch's aux bytes), per thread's range of reads, then joined
+    std::vector<pcabi_mods_read> mreads;
+    std::vector<pcabi_mods_part> mparts;
+    std::vector<int64_t> mpart0;   // a thread's first entry of mparts
+    std::vector<uint8_t> has_mods;
+    // the same for the move tables (pcabi_moves_*): vread[i] = the read's entry of vreads, -1 without one
+    std::vector<pcabi_moves_read> vreads;
+    std::vector<pcabi_moves_part> vparts;
+    std::vector<int64_t> vpart0;
+    std::vector<int32_t> vread;
+    std::vector<uint8_t> usable, vusable;
+    pcabi_internal::ModsTables mt;
+    pcabi_internal::MovesTables vt;
+    // what layout() makes
+    std::vector<pcabi_bam_part> parts;
+    std::vector<uint8_t> side;
+    std::vector<int32_t> kept;      // per part: the aux bytes that lie before its gaps
+    std::vector<int64_t> tpart0;    // a thread's first entry of parts
+    int64_t emitted = 0;
+
+    TagParts(const pcabi_reads *b_, const WriteArgs &wa_, int keep_aux, int tag_flags)
+        : b(b_), wa(wa_), have_aux(keep_aux && !b_->aux_off.empty()), remap(have_aux && keep_aux == 2),
+          keep_moves(have_aux && (tag_flags & PCABI_BAM_KEEP_MOVES)), no_qual(b_->type == PCABI_FASTA),
+          nt((int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b_->n / 512))) {}
+    bool mods() const { return !mreads.empty(); }
+    bool moves() const { return !vreads.empty(); }
+    // A part keeps its read's aux bytes verbatim when it is the whole read with the bases as stored.
+    bool verbatim(int64_t i, bool own, int64_t s0, int64_t ns) const {
+        return !own && s0 == 0 && ns == b->seq_off[i + 1] - b->seq_off[i] && b->as_stored[i];
+    }
+
+    // first pass: the tables of the tags to remap
+    void list() {
+        mpart0.assign((size_t)nt + 1, 0);
+        vpart0.assign((size_t)nt + 1, 0);
+        has_mods.assign(remap ? (size_t)b->n : 0, 0);
+        vread.assign(keep_moves ? (size_t)b->n : 0, -1);
+        if (remap || keep_moves) {
+            std::vector<std::vector<pcabi_mods_read>> t_reads((size_t)nt);
+            std::vector<std::vector<pcabi_mods_part>> t_parts((size_t)nt);
+            std::vector<std::vector<pcabi_moves_read>> t_vreads((size_t)nt);
+            std::vector<std::vector<pcabi_moves_part>> t_vparts((size_t)nt);
+            fan_out(nt, [&](int t) {
+                std::vector<std::pair<int64_t, int64_t>> rg;
+                for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
+                    int64_t mread = -2, mv = -2;   // the read's entry; -1: it carries none of the tags; -2: not looked yet
+                    read_parts(wa, i, rg, [&](const char *, size_t, bool own, int64_t s0, int64_t ns, int64_t, int64_t) {
+                        if (verbatim(i, own, s0, ns)) return;
+                        if (remap && mread == -2)
+                            mread = mods_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i],
+                                                 b->seq_off[i + 1] - b->seq_off[i], &t_reads[(size_t)t], (int64_t)t_parts[(size_t)t].size());
+                        if (keep_moves && mv == -2)
+                            mv = moves_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i + 1] - b->seq_off[i],
+                                               &t_vreads[(size_t)t], (int64_t)t_vparts[(size_t)t].size());
+                        if (keep_moves && mv >= 0) {
+                            vread[(size_t)i] = (int32_t)mv;
+                            ++t_vreads[(size_t)t][(size_t)mv].n_parts;
+                            t_vparts[(size_t)t].push_back(pcabi_moves_part{0, (int32_t)mv, (int32_t)s0, (int32_t)ns, 0});
+                        }
+                        if (!remap || mread < 0) return;
+                        has_mods[(size_t)i] = 1;
+                        ++t_reads[(size_t)t][(size_t)mread].n_parts;
+                        t_parts[(size_t)t].push_back(pcabi_mods_part{0, (int32_t)mread, (int32_t)s0, (int32_t)ns, 0});
+                    });
+                }
+            });
+            for (int t = 0; t < nt; ++t) {
+                const int64_t read_base = (int64_t)vreads.size(), part_base = (int64_t)vparts.size();
+                vpart0[(size_t)t] = part_base;
+                for (pcabi_moves_read r : t_vreads[(size_t)t]) {
+                    r.part0 += part_base;
+                    vreads.push_back(r);
+                }
+                for (pcabi_moves_part p : t_vparts[(size_t)t]) {
+                    p.read += (int32_t)read_base;
+                    vparts.push_back(p);
+                }
+                if (keep_moves)
+                    for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i)
+                        if (vread[(size_t)i] >= 0) vread[(size_t)i] += (int32_t)read_base;
+            }
+            vpart0[(size_t)nt] = (int64_t)vparts.size();
+            for (int t = 0; t < nt; ++t) {
+                const int64_t read_base = (int64_t)mreads.size(), part_base = (int64_t)mparts.size();
+                mpart0[(size_t)t] = part_base;
+                for (pcabi_mods_read r : t_reads[(size_t)t]) {
+                    r.part0 += part_base;
+                    mreads.push_back(r);
+                }
+                for (pcabi_mods_part p : t_parts[(size_t)t]) {
+                    p.read += (int32_t)read_base;
+                    mparts.push_back(p);
+                }
+            }
+            mpart0[(size_t)nt] = (int64_t)mparts.size();
+        }
+        usable.assign(mreads.size(), 0);
+        mt.tags = b->aux.data(), mt.tags_n = (int64_t)b->aux.size(), mt.reads = mreads.data(), mt.n_reads = (int64_t)mreads.size();
+        mt.parts = mparts.data(), mt.n_parts = (int64_t)mparts.size(), mt.usable = usable.data();
+        vusable.assign(vreads.size(), 0);
+        vt.tags = b->aux.data(), vt.tags_n = (int64_t)b->aux.size(), vt.reads = vreads.data(), vt.n_reads = (int64_t)vreads.size();
+        vt.parts = vparts.data(), vt.n_parts = (int64_t)vparts.size(), vt.usable = vusable.data();
+    }
+
+    // The parts and their side blob (name, then aux bytes), per thread's range of reads, then joined. With
+    // sized modification tags (mparts[].len) a gap of the tags' length follows a part's kept tags, and
+    // mparts[].out names it; a gap for a sized move table (vparts[].len, mv then ts) follows that, and a
+    // read whose ts is rewritten there loses it from the kept tags.
+    void layout() {
+        using namespace pcabi_bam;
+        std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
+        std::vector<std::vector<uint8_t>> t_side((size_t)nt);
+        std::vector<std::vector<int32_t>> t_kept((size_t)nt);
+        std::vector<int64_t> t_emit((size_t)nt, 0);
+        fan_out(nt, [&](int t) {
+            std::vector<std::pair<int64_t, int64_t>> rg;
+            std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
+            std::vector<uint8_t> &side = t_side[(size_t)t];
+            int64_t mp = mpart0[(size_t)t], vp = vpart0[(size_t)t];
+            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
+                t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+                    pcabi_bam_part p;
+                    std::memset(&p, 0, sizeof p);
+                    p.seq_src = b->seq_off[i] + s0;
+                    p.qual_src = (no_qual || nq < ns) ? -1 : b->qual_off[i] + q0;
+                    p.side_off = (int64_t)side.size();
+                    p.l_seq = (int32_t)ns;
+                    // the name: the header up to its first space or tab, at most 254 bytes, "*" when empty
+                    size_t k = 0;
+                    while (k < nn && k < (size_t)kMaxName && name[k] != ' ' && name[k] != '\t') ++k;
+                    if (k == 0) side.push_back('*'), k = 1;
+                    else side.insert(side.end(), name, name + k);
+                    p.name_len = (int32_t)k;
+                    int32_t kept_len = 0;
+                    if (have_aux) {
+                        const uint8_t *ax = b->aux.data() + b->aux_off[i];
+                        const int64_t an = b->aux_off[i + 1] - b->aux_off[i];
+                        if (verbatim(i, own, s0, ns)) {
+                            side.insert(side.end(), ax, ax + an);   // the whole read, as stored
+                            kept_len = (int32_t)an;
+                        } else {   // a changed read: without the tags that count its bases
+                            const int32_t vr = keep_moves ? vread[(size_t)i] : -1;
+                            const bool new_ts = vr >= 0 && vusable[(size_t)vr] && vreads[(size_t)vr].ts >= 0;
+                            for (int64_t at = 0; at < an;) {
+                                const int64_t nx = aux_next(ax, an, at);
+                                if (nx < 0) break;
+                                if (!aux_positional(ax + at) && !(new_ts && ax[at] == 't' && ax[at + 1] == 's'))
+                                    side.insert(side.end(), ax + at, ax + nx);
+                                at = nx;
+                            }
+                            kept_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
+                            if (remap && has_mods[(size_t)i]) {   // its remapped tags go behind them
+                                mparts[(size_t)mp].out = (int64_t)side.size();
+                                side.resize(side.size() + (size_t)mparts[(size_t)mp].len);
+                                ++mp;
+                            }
+                            if (vr >= 0) {   // and its move table behind those
+                                vparts[(size_t)vp].out = (int64_t)side.size();
+                                side.resize(side.size() + (size_t)vparts[(size_t)vp].len);
+                                ++vp;
+                            }
+                        }
+                        p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
+                    }
+                    t_kept[(size_t)t].push_back(kept_len);
+                    parts.push_back(p);
+                }) ? 1 : 0;
+            }
+        });
+        tpart0.assign((size_t)nt + 1, 0);
+        for (int t = 0; t < nt; ++t) {
+            const int64_t base = (int64_t)side.size();
+            tpart0[(size_t)t] = (int64_t)parts.size();
+            for (pcabi_bam_part p : t_parts[(size_t)t]) {
+                p.side_off += base;
+                parts.push_back(p);
+            }
+            kept.insert(kept.end(), t_kept[(size_t)t].begin(), t_kept[(size_t)t].end());
+            for (int64_t m = mpart0[(size_t)t]; m < mpart0[(size_t)t + 1]; ++m) mparts[(size_t)m].out += base;
+            for (int64_t m = vpart0[(size_t)t]; m < vpart0[(size_t)t + 1]; ++m) vparts[(size_t)m].out += base;
+            side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
+            t_side[(size_t)t] = std::vector<uint8_t>();
+            emitted += t_emit[(size_t)t];
+        }
+        tpart0[(size_t)nt] = (int64_t)parts.size();
+    }
+};
+
 }  // namespace
 
 extern "C" int pcabi_reads_write_bam(const pcabi_reads *b, const char *path, int append, const int32_t *start_trim,
@@ -1894,170 +2092,21 @@ extern "C" int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path
     g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
     const double t_begin = now_s();
     const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
-    const bool have_aux = keep_aux && !b->aux_off.empty();
-    const bool remap = have_aux && keep_aux == 2;
-    const bool keep_moves = have_aux && (tag_flags & PCABI_BAM_KEEP_MOVES);
-    const bool no_qual = b->type == PCABI_FASTA;
-    const int nt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, b->n / 512));
-    // A part keeps its read's aux bytes verbatim when it is the whole read with the bases as stored.
-    auto verbatim = [&](int64_t i, bool own, int64_t s0, int64_t ns) {
-        return !own && s0 == 0 && ns == b->seq_off[i + 1] - b->seq_off[i] && b->as_stored[i];
-    };
-    // remap, first pass: the changed reads that carry modification tags and their parts (include/pcabi.h
-    // pcabi_mods_*; the tag blob is the batch's aux bytes), per thread's range of reads, then joined
-    std::vector<pcabi_mods_read> mreads;
-    std::vector<pcabi_mods_part> mparts;
-    std::vector<int64_t> mpart0((size_t)nt + 1, 0);   // a thread's first entry of mparts
-    std::vector<uint8_t> has_mods(remap ? (size_t)b->n : 0, 0);
-    // the same for the move tables (pcabi_moves_*): vread[i] = the read's entry of vreads, -1 without one
-    std::vector<pcabi_moves_read> vreads;
-    std::vector<pcabi_moves_part> vparts;
-    std::vector<int64_t> vpart0((size_t)nt + 1, 0);
-    std::vector<int32_t> vread(keep_moves ? (size_t)b->n : 0, -1);
-    if (remap || keep_moves) {
-        std::vector<std::vector<pcabi_mods_read>> t_reads((size_t)nt);
-        std::vector<std::vector<pcabi_mods_part>> t_parts((size_t)nt);
-        std::vector<std::vector<pcabi_moves_read>> t_vreads((size_t)nt);
-        std::vector<std::vector<pcabi_moves_part>> t_vparts((size_t)nt);
-        fan_out(nt, [&](int t) {
-            std::vector<std::pair<int64_t, int64_t>> rg;
-            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
-                int64_t mread = -2, mv = -2;   // the read's entry; -1: it carries none of the tags; -2: not looked yet
-                read_parts(wa, i, rg, [&](const char *, size_t, bool own, int64_t s0, int64_t ns, int64_t, int64_t) {
-                    if (verbatim(i, own, s0, ns)) return;
-                    if (remap && mread == -2)
-                        mread = mods_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i],
-                                             b->seq_off[i + 1] - b->seq_off[i], &t_reads[(size_t)t], (int64_t)t_parts[(size_t)t].size());
-                    if (keep_moves && mv == -2)
-                        mv = moves_read_of(b->aux.data(), b->aux_off[i], b->aux_off[i + 1], b->seq_off[i + 1] - b->seq_off[i],
-                                           &t_vreads[(size_t)t], (int64_t)t_vparts[(size_t)t].size());
-                    if (keep_moves && mv >= 0) {
-                        vread[(size_t)i] = (int32_t)mv;
-                        ++t_vreads[(size_t)t][(size_t)mv].n_parts;
-                        t_vparts[(size_t)t].push_back(pcabi_moves_part{0, (int32_t)mv, (int32_t)s0, (int32_t)ns, 0});
-                    }
-                    if (!remap || mread < 0) return;
-                    has_mods[(size_t)i] = 1;
-                    ++t_reads[(size_t)t][(size_t)mread].n_parts;
-                    t_parts[(size_t)t].push_back(pcabi_mods_part{0, (int32_t)mread, (int32_t)s0, (int32_t)ns, 0});
-                });
-            }
-        });
-        for (int t = 0; t < nt; ++t) {
-            const int64_t read_base = (int64_t)vreads.size(), part_base = (int64_t)vparts.size();
-            vpart0[(size_t)t] = part_base;
-            for (pcabi_moves_read r : t_vreads[(size_t)t]) {
-                r.part0 += part_base;
-                vreads.push_back(r);
-            }
-            for (pcabi_moves_part p : t_vparts[(size_t)t]) {
-                p.read += (int32_t)read_base;
-                vparts.push_back(p);
-            }
-            if (keep_moves)
-                for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i)
-                    if (vread[(size_t)i] >= 0) vread[(size_t)i] += (int32_t)read_base;
-        }
-        vpart0[(size_t)nt] = (int64_t)vparts.size();
-        for (int t = 0; t < nt; ++t) {
-            const int64_t read_base = (int64_t)mreads.size(), part_base = (int64_t)mparts.size();
-            mpart0[(size_t)t] = part_base;
-            for (pcabi_mods_read r : t_reads[(size_t)t]) {
-                r.part0 += part_base;
-                mreads.push_back(r);
-            }
-            for (pcabi_mods_part p : t_parts[(size_t)t]) {
-                p.read += (int32_t)read_base;
-                mparts.push_back(p);
-            }
-        }
-        mpart0[(size_t)nt] = (int64_t)mparts.size();
-    }
-    const bool mods = !mreads.empty();
-    std::vector<uint8_t> usable(mreads.size());
-    pcabi_internal::ModsTables mt;
-    mt.tags = b->aux.data(), mt.tags_n = (int64_t)b->aux.size(), mt.reads = mreads.data(), mt.n_reads = (int64_t)mreads.size();
-    mt.parts = mparts.data(), mt.n_parts = (int64_t)mparts.size(), mt.usable = usable.data();
-    const bool moves = !vreads.empty();
-    std::vector<uint8_t> vusable(vreads.size());
-    pcabi_internal::MovesTables vt;
-    vt.tags = b->aux.data(), vt.tags_n = (int64_t)b->aux.size(), vt.reads = vreads.data(), vt.n_reads = (int64_t)vreads.size();
-    vt.parts = vparts.data(), vt.n_parts = (int64_t)vparts.size(), vt.usable = vusable.data();
-    std::vector<pcabi_bam_part> parts;
-    std::vector<uint8_t> side, head;
-    int64_t emitted = 0, stream_n = 0;
+    // the tables of the tags to remap (TagParts::list), then the parts and their side blob (TagParts::layout)
+    TagParts tp(b, wa, keep_aux, tag_flags);
+    tp.list();
+    const bool mods = tp.mods(), moves = tp.moves();
+    pcabi_internal::ModsTables &mt = tp.mt;
+    pcabi_internal::MovesTables &vt = tp.vt;
+    std::vector<pcabi_bam_part> &parts = tp.parts;
+    std::vector<uint8_t> &side = tp.side;
+    std::vector<uint8_t> head;
+    int64_t &emitted = tp.emitted;
+    int64_t stream_n = 0;
     PackLayout lay;
-    // The parts and their side blob (name, then aux bytes), per thread's range of reads, then joined, and the
-    // chain planned. With sized modification tags (mparts[].len) a gap of the tags' length follows a part's
-    // kept tags, and mparts[].out names it; a gap for a sized move table (vparts[].len, mv then ts) follows
-    // that, and a read whose ts is rewritten there loses it from the kept tags.
+    // the side blob (with its gaps once the tags are sized), the file header, and the chain planned
     auto layout = [&] {
-        std::vector<std::vector<pcabi_bam_part>> t_parts((size_t)nt);
-        std::vector<std::vector<uint8_t>> t_side((size_t)nt);
-        std::vector<int64_t> t_emit((size_t)nt, 0);
-        fan_out(nt, [&](int t) {
-            std::vector<std::pair<int64_t, int64_t>> rg;
-            std::vector<pcabi_bam_part> &parts = t_parts[(size_t)t];
-            std::vector<uint8_t> &side = t_side[(size_t)t];
-            int64_t mp = mpart0[(size_t)t], vp = vpart0[(size_t)t];
-            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i) {
-                t_emit[(size_t)t] += read_parts(wa, i, rg, [&](const char *name, size_t nn, bool own, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
-                    pcabi_bam_part p;
-                    std::memset(&p, 0, sizeof p);
-                    p.seq_src = b->seq_off[i] + s0;
-                    p.qual_src = (no_qual || nq < ns) ? -1 : b->qual_off[i] + q0;
-                    p.side_off = (int64_t)side.size();
-                    p.l_seq = (int32_t)ns;
-                    // the name: the header up to its first space or tab, at most 254 bytes, "*" when empty
-                    size_t k = 0;
-                    while (k < nn && k < (size_t)kMaxName && name[k] != ' ' && name[k] != '\t') ++k;
-                    if (k == 0) side.push_back('*'), k = 1;
-                    else side.insert(side.end(), name, name + k);
-                    p.name_len = (int32_t)k;
-                    if (have_aux) {
-                        const uint8_t *ax = b->aux.data() + b->aux_off[i];
-                        const int64_t an = b->aux_off[i + 1] - b->aux_off[i];
-                        if (verbatim(i, own, s0, ns)) {
-                            side.insert(side.end(), ax, ax + an);   // the whole read, as stored
-                        } else {   // a changed read: without the tags that count its bases
-                            const int32_t vr = keep_moves ? vread[(size_t)i] : -1;
-                            const bool new_ts = vr >= 0 && vusable[(size_t)vr] && vreads[(size_t)vr].ts >= 0;
-                            for (int64_t at = 0; at < an;) {
-                                const int64_t nx = aux_next(ax, an, at);
-                                if (nx < 0) break;
-                                if (!aux_positional(ax + at) && !(new_ts && ax[at] == 't' && ax[at + 1] == 's'))
-                                    side.insert(side.end(), ax + at, ax + nx);
-                                at = nx;
-                            }
-                            if (remap && has_mods[(size_t)i]) {   // its remapped tags go behind them
-                                mparts[(size_t)mp].out = (int64_t)side.size();
-                                side.resize(side.size() + (size_t)mparts[(size_t)mp].len);
-                                ++mp;
-                            }
-                            if (vr >= 0) {   // and its move table behind those
-                                vparts[(size_t)vp].out = (int64_t)side.size();
-                                side.resize(side.size() + (size_t)vparts[(size_t)vp].len);
-                                ++vp;
-                            }
-                        }
-                        p.aux_len = (int32_t)((int64_t)side.size() - p.side_off - p.name_len);
-                    }
-                    parts.push_back(p);
-                }) ? 1 : 0;
-            }
-        });
-        for (int t = 0; t < nt; ++t) {
-            const int64_t base = (int64_t)side.size();
-            for (pcabi_bam_part p : t_parts[(size_t)t]) {
-                p.side_off += base;
-                parts.push_back(p);
-            }
-            for (int64_t m = mpart0[(size_t)t]; m < mpart0[(size_t)t + 1]; ++m) mparts[(size_t)m].out += base;
-            for (int64_t m = vpart0[(size_t)t]; m < vpart0[(size_t)t + 1]; ++m) vparts[(size_t)m].out += base;
-            side.insert(side.end(), t_side[(size_t)t].begin(), t_side[(size_t)t].end());
-            t_side[(size_t)t] = std::vector<uint8_t>();
-            emitted += t_emit[(size_t)t];
-        }
+        tp.layout();
         if (!append) {
             static const char kDefault[] = "@HD\tVN:1.6\tSO:unknown\n";
             const char *text = header_text ? header_text : kDefault;
@@ -2173,6 +2222,157 @@ extern "C" int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path
     ok = (::close(fd) == 0) && ok;
     if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
     return (int)std::min<int64_t>(emitted, INT32_MAX);
+}
+
+// ---- text writer with tags in the headers ------------------------------------------------------
+// include/pcabi.h "SAM tags in FASTQ / FASTA headers": the parts, the tables and the side blob are the BAM
+// writer's (TagParts); a record's header is the text writers' name followed by the SAM text of the aux
+// bytes the BAM writer would give the part (csrc/pcabi_auxtext.h).
+extern "C" int pcabi_reads_write_tags(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                                      const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                                      const int64_t *cuts, int min_split_read_size, int discard_middle, int untrimmed,
+                                      const uint8_t *select, int gzip_device, int keep_aux, int tag_flags, int header_tags) {
+    using namespace pcabi_auxtext;
+    if (tag_flags & ~PCABI_BAM_KEEP_MOVES) return fail(PCABI_E_ARG, "unknown tag_flags");
+    if (!b || !path) return fail(PCABI_E_ARG, "bad arguments");
+    if (!header_tags || !keep_aux || b->aux_off.empty())   // nothing to carry: today's writer, byte for byte
+        return pcabi_reads_write_dev(b, path, append, gz, fasta, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle,
+                                     untrimmed, select, gzip_device);
+    if (keep_aux != 1 && keep_aux != 2) return fail(PCABI_E_ARG, "keep_aux is 0, 1 or 2");
+    const bool on_device = gz == 2 || gz == 3;
+    if (on_device && std::strcmp(path, "-") == 0) return fail(PCABI_E_ARG, "gz = 2 writes files, not stdout");
+    g_write_times[0] = g_write_times[1] = g_write_times[2] = 0;
+    const double t_begin = now_s();
+    const WriteArgs wa{b, start_trim, end_trim, cut_off, cuts, min_split_read_size, discard_middle, untrimmed, select};
+    TagParts tp(b, wa, keep_aux, tag_flags);
+    tp.list();
+    const bool mods = tp.mods(), moves = tp.moves();
+    std::vector<pcabi_fastx_part> fparts;
+    // after tp.layout(): the records' parts, in the BAM parts' order, their names (the text writers': the
+    // whole header, or the numbered copy) appended to the side blob
+    auto make_parts = [&] {
+        const int nt = tp.nt;
+        fparts.resize(tp.parts.size());
+        std::vector<std::vector<uint8_t>> t_names((size_t)nt);
+        fan_out(nt, [&](int t) {
+            std::vector<std::pair<int64_t, int64_t>> rg;
+            int64_t k = tp.tpart0[(size_t)t];
+            std::vector<uint8_t> &names = t_names[(size_t)t];
+            for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i)
+                read_parts(wa, i, rg, [&](const char *name, size_t nn, bool, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+                    const pcabi_bam_part &bp = tp.parts[(size_t)k];
+                    pcabi_fastx_part &p = fparts[(size_t)k++];
+                    std::memset(&p, 0, sizeof p);
+                    p.seq_src = b->seq_off[i] + s0, p.qual_src = b->qual_off[i] + q0;
+                    p.l_seq = (int32_t)ns, p.l_qual = fasta ? 0 : (int32_t)nq;
+                    p.name_off = (int64_t)names.size(), p.name_len = (int32_t)nn;
+                    names.insert(names.end(), name, name + nn);
+                    p.aux_off = bp.side_off + bp.name_len, p.aux_len = bp.aux_len;
+                    p.flags = b->rna[i] ? PCABI_FASTX_RNA : 0;
+                });
+        });
+        for (int t = 0; t < nt; ++t) {
+            const int64_t base = (int64_t)tp.side.size();
+            for (int64_t k = tp.tpart0[(size_t)t]; k < tp.tpart0[(size_t)t + 1]; ++k) fparts[(size_t)k].name_off += base;
+            tp.side.insert(tp.side.end(), t_names[(size_t)t].begin(), t_names[(size_t)t].end());
+        }
+    };
+    const int64_t seq_n = (int64_t)b->seq.size(), qual_n = (int64_t)b->qual.size();
+    if (on_device) {
+        const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
+        if (fd < 0) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+        bool ok = true;
+        g_write_times[0] = now_s() - t_begin;
+        const double t0 = now_s();
+        double layout_s = 0;
+        const int64_t zn = pcabi_internal::fastx_write_tags_dev(
+            gzip_device, (const uint8_t *)b->seq.data(), seq_n, (const uint8_t *)b->qual.data(), qual_n, mods ? &tp.mt : nullptr,
+            moves ? &tp.vt : nullptr, fasta != 0, gz == 3,
+            [&](pcabi_internal::FastxWriteJob *job) {
+                const double t1 = now_s();
+                tp.layout();
+                make_parts();
+                layout_s = now_s() - t1;
+                job->side = tp.side.data(), job->side_n = (int64_t)tp.side.size();
+                job->parts = fparts.data(), job->kept = tp.kept.data(), job->n_parts = (int64_t)fparts.size();
+            },
+            [&](const uint8_t *p, int64_t n) {
+                const double t1 = now_s();
+                ok = ok && write_all(fd, p, (size_t)n);
+                g_write_times[2] += now_s() - t1;
+            });
+        ok = (::close(fd) == 0) && ok;
+        if (zn < 0) return (int)zn;
+        g_write_times[0] += layout_s;
+        g_write_times[1] = now_s() - t0 - g_write_times[2] - layout_s;
+        if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
+        return (int)std::min<int64_t>(tp.emitted, INT32_MAX);
+    }
+    // the host build: the remapped tags sized and written as the BAM writer's host path does
+    pcabi_internal::ModsHost *keep = mods ? pcabi_internal::mods_host_new() : nullptr;
+    pcabi_internal::MovesHost *vkeep = moves ? pcabi_internal::moves_host_new() : nullptr;
+    int rc = 0;
+    if (mods)
+        rc = pcabi_internal::mods_plan_any(-1, nullptr, keep, nullptr, (const uint8_t *)b->seq.data(), nullptr, seq_n, tp.mt.tags, tp.mt.tags_n,
+                                           tp.mt.reads, tp.mt.n_reads, tp.mt.parts, tp.mt.n_parts, tp.mt.usable);
+    if (!rc && moves) rc = pcabi_internal::moves_plan_host(vkeep, tp.vt);
+    if (!rc) {
+        tp.layout();
+        if (mods)
+            pcabi_internal::mods_write_host(keep, (const uint8_t *)b->seq.data(), tp.mt.tags, tp.mt.reads, tp.mt.n_reads, tp.mt.parts,
+                                            tp.mt.n_parts, tp.side.data());
+        if (moves) pcabi_internal::moves_write_host(vkeep, tp.vt, tp.side.data());
+    }
+    if (keep) pcabi_internal::mods_host_free(keep);
+    if (vkeep) pcabi_internal::moves_host_free(vkeep);
+    if (rc) return rc;
+    make_parts();
+    const int64_t np = (int64_t)fparts.size();
+    std::vector<pcabi_auxtext_part> ap((size_t)np);
+    for (int64_t k = 0; k < np; ++k) ap[(size_t)k] = pcabi_auxtext_part{fparts[(size_t)k].aux_off, 0, 0, fparts[(size_t)k].aux_len, 0};
+    if ((rc = pcabi_auxtext_plan(-1, tp.side.data(), (int64_t)tp.side.size(), ap.data(), np))) return rc;
+    FastxLayout lay;
+    lay.fasta = fasta != 0;
+    for (int64_t k = 0; k < np; ++k) {
+        fparts[(size_t)k].text_len = ap[(size_t)k].len > 0 ? ap[(size_t)k].len : 0;
+        lay.place(&fparts[(size_t)k]);
+    }
+    std::vector<uint8_t, NoInit<uint8_t>> out;
+    out.resize((size_t)lay.out);
+    {
+        const int pt = (int)std::min<int64_t>((int64_t)io_threads(), std::max<int64_t>(1, lay.out >> 20));
+        std::atomic<int64_t> next{0};
+        fan_out(pt, [&](int) {
+            for (int64_t i0; (i0 = next.fetch_add(256)) < np;)
+                for (int64_t i = i0; i < std::min(np, i0 + 256); ++i)
+                    pack_part(fparts[(size_t)i], fasta != 0, (const uint8_t *)b->seq.data(), (const uint8_t *)b->qual.data(), tp.side.data(),
+                              out.data());
+        });
+    }
+    g_write_times[0] = now_s() - t_begin;
+    const double t0 = now_s();
+    bool ok = true;
+    if (gz != 0) {
+        gzFile g = gzopen(path, append ? "ab" : "wb");
+        if (!g) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+        for (size_t k = 0; ok && k < out.size();) {
+            const unsigned piece = (unsigned)std::min<size_t>(out.size() - k, 256u << 20);
+            ok = gzwrite(g, out.data() + k, piece) == (int)piece;
+            k += piece;
+        }
+        ok = (gzclose(g) == Z_OK) && ok;
+    } else if (std::strcmp(path, "-") == 0) {
+        ok = std::fwrite(out.data(), 1, out.size(), stdout) == out.size();
+        std::fflush(stdout);
+    } else {
+        const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0666);
+        if (fd < 0) return fail(PCABI_E_ARG, std::string("could not write ") + path);
+        ok = write_all(fd, out.data(), out.size());
+        ok = (::close(fd) == 0) && ok;
+    }
+    g_write_times[2] = now_s() - t0;
+    if (!ok) return fail(PCABI_E_ARG, std::string("write failed: ") + path);
+    return (int)std::min<int64_t>(tp.emitted, INT32_MAX);
 }
 
 extern "C" int64_t pcabi_gzip_plan_lines(const char *text, int64_t n, int64_t long_line, int64_t cap,

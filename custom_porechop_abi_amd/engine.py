@@ -971,3 +971,97 @@ def moves_counts(reset=False):
     v = np.zeros(2, np.int64)
     lib().pcabi_moves_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
     return int(v[0]), int(v[1])
+
+
+# ---- SAM tags in FASTQ / FASTA headers (csrc/pcabi_auxtext.h, csrc/pcabi_auxtext.hip) ---------------
+# include/pcabi.h pcabi_auxtext_part, pcabi_fastx_part
+AUXTEXT_PART = np.dtype([('aux_off', np.int64), ('out', np.int64), ('len', np.int64), ('aux_len', np.int32),
+                         ('reserved', np.int32)])
+FASTX_PART = np.dtype([('seq_src', np.int64), ('qual_src', np.int64), ('name_off', np.int64), ('aux_off', np.int64),
+                       ('text_len', np.int64), ('out', np.int64), ('tile0', np.int64), ('l_seq', np.int32),
+                       ('l_qual', np.int32), ('name_len', np.int32), ('aux_len', np.int32), ('flags', np.int32),
+                       ('reserved', np.int32)])
+FASTX_RNA = 1
+assert AUXTEXT_PART.itemsize == 32 and FASTX_PART.itemsize == 80
+
+
+def _bytes_arg(a):
+    return np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, np.uint8)
+
+
+def auxtext_plan(aux, parts, device=0):
+    """The length of every chain's SAM text (pcabi_auxtext_plan): on GPU `device`, or with the host
+    build of the same code when device < 0. aux: the bytes the C-contiguous AUXTEXT_PART array `parts`
+    indexes (aux_off / aux_len set); 'len' is filled in place, -1 for a chain that does not walk.
+    Adds the tags to auxtext_counts(). Returns parts."""
+    aux = _bytes_arg(aux)
+    if parts.dtype != AUXTEXT_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('auxtext_plan: parts is a C-contiguous AUXTEXT_PART array')
+    rc = lib().pcabi_auxtext_plan(int(device), _ptr(aux), aux.size, _ptr(parts), parts.size)
+    check(int(rc), 'pcabi_auxtext_plan')
+    return parts
+
+
+def auxtext_write(aux, parts, out, device=0):
+    """Every chain's text written to out[part.out, part.out + part.len) (pcabi_auxtext_write): parts as
+    auxtext_plan left them, with 'out' set; out: a C-contiguous uint8 array, filled in place (bytes no
+    part owns keep their values) and returned."""
+    aux = _bytes_arg(aux)
+    parts = np.ascontiguousarray(parts, AUXTEXT_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('auxtext_write: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_auxtext_write(int(device), _ptr(aux), aux.size, _ptr(parts), parts.size, _ptr(out), out.size)
+    check(int(rc), 'pcabi_auxtext_write')
+    return out
+
+
+def auxtext_counts(reset=False):
+    """(tags written as text, tags left out) since the last reset (pcabi_auxtext_counts)."""
+    v = np.zeros(2, np.int64)
+    lib().pcabi_auxtext_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
+    return int(v[0]), int(v[1])
+
+
+def aux_text(aux_chains, device=None):
+    """The SAM text of each aux chain (a list of bytes): tab-separated TG:T:value fields, b'' for a
+    chain without tags, None for a chain that does not walk. device None or < 0: the host build."""
+    dev = -1 if device is None else int(device)
+    chains = [bytes(c) for c in aux_chains]
+    parts = np.zeros(len(chains), AUXTEXT_PART)
+    parts['aux_len'] = [len(c) for c in chains]
+    parts['aux_off'][1:] = np.cumsum(parts['aux_len'][:-1], dtype=np.int64)
+    blob = b''.join(chains)
+    auxtext_plan(blob, parts, dev)
+    lens = np.maximum(parts['len'], 0)
+    parts['out'][1:] = np.cumsum(lens[:-1], dtype=np.int64)
+    out = np.zeros(int(lens.sum()), np.uint8)
+    auxtext_write(blob, parts, out, dev)
+    buf = out.tobytes()
+    return [None if p['len'] < 0 else buf[int(p['out']):int(p['out']) + int(p['len'])] for p in parts]
+
+
+def fastx_pack_plan(parts, fasta=False, out0=0):
+    """Output offsets and tiles of a FASTX_PART table (pcabi_fastx_pack_plan): fills parts['out'] and
+    parts['tile0'] in place for records that start at out0; returns (the end, tiles)."""
+    if parts.dtype != FASTX_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('fastx_pack_plan: parts is a C-contiguous FASTX_PART array')
+    tiles = np.zeros(1, np.int64)
+    end = lib().pcabi_fastx_pack_plan(_ptr(parts), parts.size, int(bool(fasta)), int(out0), _ptr(tiles))
+    if end < 0:
+        check(int(end), 'pcabi_fastx_pack_plan')
+    return int(end), int(tiles[0])
+
+
+def fastx_pack(seq, qual, side, parts, out, fasta=False, device=0):
+    """The parts of a planned table laid out as FASTQ / FASTA records in `out`, their aux chains' SAM
+    text in the headers (pcabi_fastx_pack_host): on GPU `device`, or with the host build of the same
+    code when device < 0. side: the names and the aux chains; out: a C-contiguous uint8 array, filled
+    in place (bytes no part owns keep their values) and returned."""
+    arrs = [_bytes_arg(a) for a in (seq, qual, side)]
+    parts = np.ascontiguousarray(parts, FASTX_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('fastx_pack: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_fastx_pack_host(int(device), _ptr(arrs[0]), arrs[0].size, _ptr(arrs[1]), arrs[1].size, _ptr(arrs[2]),
+                                     arrs[2].size, _ptr(parts), parts.size, int(bool(fasta)), _ptr(out), out.size)
+    check(int(rc), 'pcabi_fastx_pack_host')
+    return out

@@ -548,7 +548,7 @@ def get_albacore_barcode_from_path(albacore_path):
 def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None, middle_cuts=None,
                 min_split_read_size=1000, discard_middle=False, untrimmed=False, select=None, append=False,
                 cut_arrays=None, gzip_device=None, bgzf=False, bam_header=None, keep_aux=False, keep_mods=False,
-                keep_moves=False):
+                keep_moves=False, header_tags=False):
     """NanoporeRead.get_fasta / get_fastq for every read of a ReadBatch, natively
     (pcabi_reads_write). Returns how many reads produced output (a non-empty read string). out_format: 'fasta' | 'fastq' | 'fasta.gz' | 'fastq.gz'.
     gzip_device: None compresses a '.gz' format with zlib on the host; a device index compresses it on
@@ -572,6 +572,15 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     moved along (include/pcabi.h "move tables"), behind the other tags and MM ML MN; a read whose table
     is not usable loses mv as before and keeps its ts; engine.moves_counts() tells how many went which
     way. Direct-RNA move tables (which run against the sequence) and the sp / pi tags are not handled.
+    header_tags (the four text formats, with keep_aux; pcabi_reads_write_tags): every record's header is
+    its name followed by the SAM text (tab-separated TG:T:value fields, what `samtools fastq -T` writes
+    and `minimap2 -y` reads) of the aux bytes out_format 'bam' would give the same part with the same
+    keep_aux / keep_mods / keep_moves, which are accepted for a text format only together with it. A
+    '.gz' format with gzip_device lays the text out and compresses it on that GPU; every other case
+    builds it on the host; both give the same decompressed bytes. A batch without aux bytes writes what
+    it writes without header_tags. engine.auxtext_counts() tells how many tags were written and how
+    many were left out (a name outside [A-Za-z][A-Za-z0-9], an A / Z / H value with a byte outside
+    0x20..0x7E).
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's
     middle_trim_positions as ranges), or None; cut_arrays: the same as (cut_off int64 [n + 1],
     cuts int64 [2 * n_cuts]) arrays."""
@@ -600,9 +609,13 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
     if bgzf and not (gz and gzip_device is not None):
         raise ValueError("bgzf applies to a '.gz' format compressed on a device (gzip_device)")
-    if keep_mods and not (keep_aux and out_format == 'bam'):
+    if header_tags and out_format == 'bam':
+        raise ValueError("header_tags applies to the text formats: out_format 'bam' carries its tags itself")
+    if header_tags and not keep_aux:
+        raise ValueError('header_tags needs keep_aux')
+    if keep_mods and not (keep_aux and (out_format == 'bam' or header_tags)):
         raise ValueError("keep_mods applies to out_format 'bam' with keep_aux")
-    if keep_moves and not (keep_aux and out_format == 'bam'):
+    if keep_moves and not (keep_aux and (out_format == 'bam' or header_tags)):
         raise ValueError("keep_moves applies to out_format 'bam' with keep_aux")
     if out_format == 'bam':
         hdr = None if bam_header is None else bytes(bam_header)
@@ -620,6 +633,15 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
                                      -1 if gzip_device is None else int(gzip_device))
         if rc < 0:
             check(rc, 'pcabi_reads_write_bam')
+        return int(rc)
+    if header_tags:
+        mode = (3 if bgzf else 2) if (gz and gzip_device is not None) else int(gz)
+        rc = L.pcabi_reads_write_tags(batch._h, os.fsencode(path), int(append), mode, int(fasta), p(st), p(et), p(co), p(cu),
+                                      int(min_split_read_size), int(discard_middle), int(untrimmed), p(sel),
+                                      -1 if gzip_device is None else int(gzip_device), 2 if keep_mods else 1,
+                                      1 if keep_moves else 0, 1)
+        if rc < 0:
+            check(rc, 'pcabi_reads_write_tags')
         return int(rc)
     if gz and gzip_device is not None:
         rc = L.pcabi_reads_write_dev(batch._h, os.fsencode(path), int(append), 3 if bgzf else 2, int(fasta), p(st), p(et), p(co),

@@ -43,10 +43,14 @@ def _finish_mode(trimmer, out_format):
 
 def _bam_kw(trimmer, out_format, b):
     """misc.write_reads' BAM arguments for batch b: the input's header text when it was BAM, and the
-    trimmer's keep_tags, keep_mods and keep_moves."""
-    if out_format != 'bam':
-        return {}
+    trimmer's keep_tags, keep_mods and keep_moves; for a text format with header_tags, the same tag
+    options and header_tags (misc.write_reads)."""
     keep = bool(getattr(trimmer, 'keep_tags', False))
+    if out_format != 'bam':
+        if not (keep and getattr(trimmer, 'header_tags', False)):
+            return {}
+        return {'keep_aux': True, 'header_tags': True, 'keep_mods': bool(getattr(trimmer, 'keep_mods', False)),
+                'keep_moves': bool(getattr(trimmer, 'keep_moves', False))}
     return {'bam_header': getattr(b, 'bam_header', None), 'keep_aux': keep,
             'keep_mods': keep and bool(getattr(trimmer, 'keep_mods', False)),
             'keep_moves': keep and bool(getattr(trimmer, 'keep_moves', False))}
@@ -68,6 +72,7 @@ class FileTrimmer(object):
     keep_tags = False                     # BAM to BAM: aux tags are dropped (set by __init__)
     keep_mods = False                     # with keep_tags: MM ML MN of changed reads are dropped, not remapped
     keep_moves = False                    # with keep_tags: mv of changed reads is dropped, ts copied
+    header_tags = False                   # with keep_tags: text outputs carry no tags in their headers
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
@@ -75,8 +80,14 @@ class FileTrimmer(object):
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
-                 keep_mods=False, keep_moves=False, gunzip_plain=False):
+                 keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False):
         self.L = L = lib()
+        # header_tags: a text output format carries each part's tags in its header as SAM text
+        # (misc.write_reads header_tags), the bins' writers included; gzip_on_device lays the text out on
+        # the device
+        if header_tags and not keep_tags:
+            raise ValueError('header_tags needs keep_tags')
+        self.header_tags = bool(header_tags)
         # out_format 'bam' from a BAM input: the records' aux tags are read and written (misc.write_reads
         # keep_aux: verbatim on reads written whole and as stored, without the position-dependent tags
         # MM ML MN Mm Ml mv, which are dropped and not recomputed, on changed reads)
@@ -339,7 +350,8 @@ class FileTrimmer(object):
                 # parse and the last write are small, so they overlap the other stages
                 for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True,
                                            gunzip_device=getattr(self, 'gunzip_device', None),
-                                           keep_aux=out_format == 'bam' and bool(getattr(self, 'keep_tags', False)),
+                                           keep_aux=bool(getattr(self, 'keep_tags', False)) and
+                                           (out_format == 'bam' or bool(getattr(self, 'header_tags', False))),
                                            gunzip_plain=bool(getattr(self, 'gunzip_plain', False))):
                     yield b, alb
                 if getattr(self, 'gunzip_plain', False):

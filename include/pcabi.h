@@ -1144,6 +1144,105 @@ int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path, int appen
                                int min_split_read_size, int discard_middle, int untrimmed, const uint8_t *select,
                                const char *header_text, int64_t header_len, int keep_aux, int tag_flags, int device);
 
+/* ---- SAM tags in FASTQ / FASTA headers (csrc/pcabi_auxtext.h, csrc/pcabi_auxtext.hip) ----------
+ * The text writers can carry a part's aux tags in its header, as `samtools fastq -T` writes them and
+ * `minimap2 -y` reads them: tab-separated TG:T:value fields behind the name. The tags are the aux bytes
+ * pcabi_reads_write_bam_tags would put into the same part's record (same keep_aux, same tag_flags), so
+ * a trimmed read or a split piece carries MM ML MN mv ts remapped exactly as in BAM output.
+ * SAM text of an aux chain: per tag a tab, the two name bytes, ':', then by type
+ *   A            A: and the byte
+ *   c C s S i I  i: and the decimal value
+ *   f            f: and C's printf("%g") of the float32 widened to double
+ *   Z, H         Z: / H: and the bytes up to the NUL
+ *   B            B:, the subtype letter as stored, then ',' and the value per element (an empty array
+ *                is TG:B:c with nothing behind it)
+ * A chain without tags adds nothing, not even a tab. A tag is left out (and counted) when its name is
+ * not [A-Za-z][A-Za-z0-9] or its A / Z / H value holds a byte outside 0x20..0x7E. A chain that does not
+ * walk -- an unknown type or subtype, a Z / H without its NUL inside the chain, a value or an array
+ * that runs past the end -- has no text: its length is -1 and nothing is written for it.
+ *   pcabi_auxtext_part : one chain aux[aux_off, aux_off + aux_len); len = its text's length (leading
+ *       tabs included), out = where the text goes.
+ *   pcabi_auxtext_plan  : fills parts[].len (-1: the chain does not walk) and adds the tags to the
+ *       counters. device >= 0: the blob and the table go up with a table of the floats' texts (the host
+ *       prints them, 16 bytes a float), k_auxtext_size walks one chain per wave and 16 bytes a part come
+ *       back; device < 0: the host build of the same code (no GPU needed). A part outside the blob is
+ *       refused (PCABI_E_ARG).
+ *   pcabi_auxtext_write : writes every part's text to out[part.out, part.out + part.len). A len that
+ *       is not what the plan gives, ranges that overlap or lie outside out[0, out_cap) are refused
+ *       (PCABI_E_ARG). On the device the output lies between 64 guard bytes, checked after the kernel
+ *       (PCABI_E_DEVICE if it wrote outside). Bytes no part owns keep their values.
+ *   pcabi_auxtext_counts : tags written as text and tags left out, as pcabi_auxtext_plan and
+ *       pcabi_reads_write_tags counted them since the last call with reset != 0.
+ *   pcabi_fastx_part : one output record. FASTQ: '@' name tag-text '\n' bases '\n' '+' '\n' qualities
+ *       '\n'; FASTA: '>' name tag-text '\n', then the bases in lines of 70, each followed by '\n'. The
+ *       name and the aux chain lie in a side blob; text_len is the chain's length from the plan (<= 0:
+ *       no tag text); PCABI_FASTX_RNA writes T as U.
+ *   pcabi_fastx_pack_plan : (host) fills out / tile0 for a chain of records that starts at out0 and
+ *       returns its end; tiles[0] (may be NULL) = the tile count. Every part owns max(1, ceil(l_seq /
+ *       16384)) tiles.
+ *   pcabi_fastx_pack_dev  : device pointers on the current device, asynchronous on `stream`: the parts
+ *       (a planned table) written into out[0, out_cap) by k_fastx_pack; the workgroup of a part's first
+ *       tile also writes its header. ftext / fslot0 / n_slots: the floats' texts (16-byte slots: the
+ *       length, then the characters) and every part's first slot, or NULL / NULL / 0 when no chain
+ *       holds a float. A part that does not lie inside the buffers writes nothing.
+ *   pcabi_fastx_pack_host : the same with host buffers, staged through the device; device < 0 runs the
+ *       host build. Parts outside the buffers, not planned, or with a text_len that is not the plan's
+ *       are refused (PCABI_E_ARG). On the device the output lies between 64 guard bytes, checked after
+ *       the kernel. Bytes no part owns keep their values.
+ *   pcabi_auxtext_last_times : on != 0 makes the device path of pcabi_reads_write_tags time its
+ *       kernels with device events; ms[0..1] = milliseconds of k_auxtext_size and k_fastx_pack,
+ *       bytes[0..1] = what they read and wrote, since the last call with reset != 0.
+ *   pcabi_reads_write_tags : pcabi_reads_write_dev with keep_aux (1, 2), tag_flags
+ *       (PCABI_BAM_KEEP_MOVES) and header_tags. header_tags == 0, keep_aux == 0 or a batch without aux
+ *       bytes: exactly pcabi_reads_write_dev. Else every record's header is the name as the text writers
+ *       write it followed by the SAM text above of the part's aux bytes. gz = 0 / 1: the host build
+ *       builds the text. gz = 2 / 3: on device gzip_device (-1: the current device) the remapped tags
+ *       are sized and written into the device copy of the side blob as for BAM output, k_auxtext_size
+ *       gives every part's text length, the host plans the records' offsets and the line-aligned
+ *       deflate blocks (pcabi_gzip_plan_lines' rules) from the line lengths alone, k_fastx_pack lays the
+ *       text out in device memory and the gzip / BGZF encoder compresses it there; only compressed
+ *       bytes come back. Both paths decompress to the same bytes.
+ * Out of scope: reading tags back from header comments; the sp / pi tags of split reads; direct-RNA
+ * move tables; escaping the tags that are left out.
+ */
+#define PCABI_FASTX_RNA 1 /* pcabi_fastx_part flags: T is written as U */
+typedef struct pcabi_auxtext_part {
+    int64_t aux_off; /* the chain in the aux blob                        */
+    int64_t out;     /* where its text goes                              */
+    int64_t len;     /* the text's length (pcabi_auxtext_plan), -1: none */
+    int32_t aux_len;
+    int32_t reserved;
+} pcabi_auxtext_part;
+typedef struct pcabi_fastx_part {
+    int64_t seq_src;  /* base 0 in the sequence buffer                         */
+    int64_t qual_src; /* quality 0 in the quality buffer (FASTQ)               */
+    int64_t name_off; /* the name (name_len bytes) in the side blob            */
+    int64_t aux_off;  /* the aux chain (aux_len bytes) in the side blob        */
+    int64_t text_len; /* the chain's text length (pcabi_auxtext_plan); <= 0: none */
+    int64_t out;      /* the record's first byte in the output                 */
+    int64_t tile0;    /* tiles of the parts before this one                    */
+    int32_t l_seq, l_qual, name_len, aux_len;
+    int32_t flags;    /* PCABI_FASTX_RNA                                       */
+    int32_t reserved;
+} pcabi_fastx_part;
+int pcabi_auxtext_plan(int device, const uint8_t *aux, int64_t aux_n, pcabi_auxtext_part *parts, int64_t n_parts);
+int pcabi_auxtext_write(int device, const uint8_t *aux, int64_t aux_n, const pcabi_auxtext_part *parts, int64_t n_parts,
+                        uint8_t *out, int64_t out_cap);
+void pcabi_auxtext_counts(int reset, int64_t *tags_written, int64_t *tags_left_out);
+void pcabi_auxtext_last_times(int on, int reset, double *ms, int64_t *bytes);
+int64_t pcabi_fastx_pack_plan(pcabi_fastx_part *parts, int64_t n_parts, int fasta, int64_t out0, int64_t *tiles);
+int pcabi_fastx_pack_dev(void *stream, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                         const uint8_t *side, int64_t side_n, const pcabi_fastx_part *parts, int64_t n_parts,
+                         int64_t n_tiles, int fasta, const uint8_t *ftext, const int64_t *fslot0, int64_t n_slots,
+                         uint8_t *out, int64_t out_cap);
+int pcabi_fastx_pack_host(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n,
+                          const uint8_t *side, int64_t side_n, const pcabi_fastx_part *parts, int64_t n_parts, int fasta,
+                          uint8_t *out, int64_t out_cap);
+int pcabi_reads_write_tags(const pcabi_reads *b, const char *path, int append, int gz, int fasta,
+                           const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
+                           const int64_t *cuts, int min_split_read_size, int discard_middle, int untrimmed,
+                           const uint8_t *select, int gzip_device, int keep_aux, int tag_flags, int header_tags);
+
 #ifdef __cplusplus
 }
 #endif
