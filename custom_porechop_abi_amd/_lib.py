@@ -181,6 +181,11 @@ def lib():
         'pcabi_fastx_pack_host': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_int, c_p, c_i64], c_int),
         'pcabi_reads_write_tags': ([c_p, ctypes.c_char_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_int,
                                     c_int, c_int, c_int], c_int),
+        'pcabi_auxparse_plan': ([c_int, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_auxparse_write': ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64], c_int),
+        'pcabi_auxparse_counts': ([c_int, c_p, c_p], None),
+        'pcabi_auxparse_last_times': ([c_int, c_int, c_p, c_p], None),
+        'pcabi_fastx_header_tags': ([c_p, c_int, c_int], c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -229,7 +234,8 @@ def exported_symbols():
             'pcabi_gunzip_stream_tune', 'pcabi_gunzip_stream_last_stats', 'pcabi_gunzip_stream_last_times',
             'pcabi_fastx_open_dev2', 'pcabi_auxtext_plan', 'pcabi_auxtext_write', 'pcabi_auxtext_counts',
             'pcabi_auxtext_last_times', 'pcabi_fastx_pack_plan', 'pcabi_fastx_pack_dev', 'pcabi_fastx_pack_host',
-            'pcabi_reads_write_tags']
+            'pcabi_reads_write_tags', 'pcabi_auxparse_plan', 'pcabi_auxparse_write', 'pcabi_auxparse_counts',
+            'pcabi_auxparse_last_times', 'pcabi_fastx_header_tags']
 
 
 class CrossRegion(ctypes.Structure):

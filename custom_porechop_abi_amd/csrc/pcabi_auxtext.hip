@@ -205,36 +205,10 @@ __global__ __launch_bounds__(kPackLanes) void k_fastx_pack(const uint8_t *__rest
 std::atomic<int64_t> g_written{0}, g_left_out{0};
 
 // ---- device-event timing (tools/header_tags_timing.py) ----
-std::mutex g_prof_mu;
-bool g_prof = false;
-double g_ms[2] = {0, 0};
-int64_t g_bytes[2] = {0, 0};
-struct Span {
-    hipEvent_t a = nullptr, b = nullptr;
-    bool on = false;
-    void begin(hipStream_t st) {
-        {
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            on = g_prof;
-        }
-        if (!on) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, st) != hipSuccess) on = false;
-    }
-    void end(hipStream_t st) {
-        if (on && hipEventRecord(b, st) != hipSuccess) on = false;
-    }
-    // the stream is idle
-    void harvest(int kind, int64_t bytes) {
-        float ms = 0;
-        if (on && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) {
-            std::lock_guard<std::mutex> lk(g_prof_mu);
-            g_ms[kind] += ms;
-            g_bytes[kind] += bytes;
-        }
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        a = b = nullptr, on = false;
-    }
+KernelTimes g_times;
+struct Span : EventSpan {
+    void begin(hipStream_t st) { EventSpan::begin(g_times, st); }
+    void harvest(int kind, int64_t bytes) { EventSpan::harvest(g_times, kind, bytes); }
 };
 
 // The floats' texts of the chains aux[off[i], off[i] + len[i]) (the host prints them): slot0[i] = part i's
@@ -326,14 +300,6 @@ int launch_pack(hipStream_t st, const uint8_t *seq, int64_t seq_n, const uint8_t
                        n_parts, n_tiles, fasta, ftext, fslot0, n_slots, out, out_cap);
     PCABI_TRY(hipGetLastError());
     return 0;
-}
-
-// no two of the spans [first, second) may meet
-bool spans_disjoint(std::vector<std::pair<int64_t, int64_t>> &spans) {
-    std::sort(spans.begin(), spans.end());
-    for (size_t k = 1; k < spans.size(); ++k)
-        if (spans[k].first < spans[k - 1].second) return false;
-    return true;
 }
 
 // The writer's block list from line lengths alone: pcabi_deflate::plan_blocks' rules (a line counts with
@@ -592,13 +558,7 @@ void pcabi_auxtext_counts(int reset, int64_t *tags_written, int64_t *tags_left_o
 }
 
 void pcabi_auxtext_last_times(int on, int reset, double *ms, int64_t *bytes) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof = on != 0;
-    for (int k = 0; k < 2; ++k) {
-        if (ms) ms[k] = g_ms[k];
-        if (bytes) bytes[k] = g_bytes[k];
-        if (reset) g_ms[k] = 0, g_bytes[k] = 0;
-    }
+    g_times.last(on, reset, ms, bytes);
 }
 
 int64_t pcabi_fastx_pack_plan(pcabi_fastx_part *parts, int64_t n_parts, int fasta, int64_t out0, int64_t *tiles) {

@@ -1,5 +1,5 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_auxparse.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
 // the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
 // pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
 // compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
@@ -11,8 +11,10 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/pcabi.h"
@@ -81,6 +83,14 @@ struct Owned {
     operator T *() const { return p; }
 };
 
+// no two of the spans [first, second) may meet (the outputs of a table's parts); sorts them
+inline bool spans_disjoint(std::vector<std::pair<int64_t, int64_t>> &spans) {
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); ++k)
+        if (spans[k].first < spans[k - 1].second) return false;
+    return true;
+}
+
 // may kept buffers serve a call that needs these sizes? holds(owner, need, owner, need, ...)
 inline bool holds() { return true; }
 template <class O, class... Rest>
@@ -142,6 +152,51 @@ struct Stream {
         s = nullptr;
     }
     operator hipStream_t() const { return s; }
+};
+
+// Device-event timing of a unit's two kernels (its timing tool's *_last_times entry): off by default.
+struct KernelTimes {
+    std::mutex mu;
+    bool on = false;
+    double ms[2] = {0, 0};
+    int64_t bytes[2] = {0, 0};
+    // the entry point: sets the switch, reports the sums (null pointers: not wanted), clears them
+    void last(int on_, int reset, double *ms_out, int64_t *bytes_out) {
+        std::lock_guard<std::mutex> lk(mu);
+        on = on_ != 0;
+        for (int k = 0; k < 2; ++k) {
+            if (ms_out) ms_out[k] = ms[k];
+            if (bytes_out) bytes_out[k] = bytes[k];
+            if (reset) ms[k] = 0, bytes[k] = 0;
+        }
+    }
+};
+// events around one kernel on a stream; harvest (the stream idle) adds the time to sum `kind`
+struct EventSpan {
+    hipEvent_t a = nullptr, b = nullptr;
+    bool on = false;
+    void begin(KernelTimes &t, hipStream_t st) {
+        {
+            std::lock_guard<std::mutex> lk(t.mu);
+            on = t.on;
+        }
+        if (!on) return;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, st) != hipSuccess) on = false;
+    }
+    void end(hipStream_t st) {
+        if (on && hipEventRecord(b, st) != hipSuccess) on = false;
+    }
+    void harvest(KernelTimes &t, int kind, int64_t n) {
+        float ms = 0;
+        if (on && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) {
+            std::lock_guard<std::mutex> lk(t.mu);
+            t.ms[kind] += ms;
+            t.bytes[kind] += n;
+        }
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        a = b = nullptr, on = false;
+    }
 };
 #endif
 
@@ -292,5 +347,18 @@ struct FastxWriteJob {
 int64_t fastx_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables *mods,
                              const MovesTables *moves, bool fasta, bool bgzf, const std::function<void(FastxWriteJob *)> &layout,
                              const std::function<void(const uint8_t *, int64_t)> &sink);
+
+// ---- pcabi_auxparse.hip --------------------------------------------------------------------------
+// The device side of a reader that parses its headers' tags (pcabi_fastx_header_tags): a stream and the
+// buffers kept between batches.
+struct AuxParseDev;
+AuxParseDev *auxparse_dev_new();
+void auxparse_dev_free(AuxParseDev *d);
+// The chains of the n headers text[off[i], off[i + 1]), back to back in *aux with their offsets in
+// *aux_off (n + 1 entries); counts the tags. device >= 0: the blob goes up once, both kernels run on d's
+// stream, the chains and the floats' fix-ups come back; device < 0: the host build on the io threads
+// (d may be null).
+int auxparse_headers(int device, AuxParseDev *d, const uint8_t *text, const int64_t *off, int64_t n, std::vector<uint8_t> *aux,
+                     std::vector<int64_t> *aux_off);
 
 }  // namespace pcabi_internal

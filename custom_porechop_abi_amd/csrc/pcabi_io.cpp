@@ -142,6 +142,10 @@ struct pcabi_fastx {
     bool fa_have_name = false;     // a header was seen (its name may be empty)
     std::string fa_name, fa_seq;
     int txt_named = -1;            // pcabi_fastx_next_text: the last header had a name (1), none (0), no header (-1)
+    // pcabi_fastx_header_tags: every batch's aux bytes are parsed from its headers, on tags_device (< 0: the host build)
+    bool header_tags = false;
+    int tags_device = -1;
+    pcabi_internal::AuxParseDev *tags_dev = nullptr;
 };
 
 // Large batch buffers (>= 8 MB, r05) come from anonymous mappings with transparent huge pages and
@@ -268,6 +272,9 @@ struct pcabi_reads {
     // empty otherwise (aux_off too)
     std::vector<uint8_t> aux, as_stored;
     std::vector<int64_t> aux_off;
+    // a FASTA / FASTQ reader with pcabi_fastx_header_tags: the aux bytes were parsed from the headers, which
+    // still hold them as text behind their first tab
+    bool tags_from_headers = false;
 };
 
 namespace {
@@ -831,6 +838,7 @@ void pcabi_fastx_close(pcabi_fastx *r) {
     }
     if (r->dev) pcabi_internal::gunzip_reader_close(r->dev);
     if (r->zs) pcabi_internal::gzstream_reader_close(r->zs);
+    pcabi_internal::auxparse_dev_free(r->tags_dev);
     if (r->zmap) munmap(r->zmap, r->zmap_len);
     r->ahead_stop = true;                 // the populate-ahead helper leaves the mapping first
     if (r->ahead.joinable()) r->ahead.join();
@@ -945,6 +953,15 @@ int64_t pcabi_fastx_next(pcabi_fastx *r, int64_t max_reads, int64_t max_bases, p
     if (r->err) {
         delete b;
         return PCABI_E_PARSE;   // the message is pcabi_last_error()'s (next_line)
+    }
+    if (r->header_tags) {   // the headers' tags as aux bytes, where a BAM reader puts a record's
+        if (const int rc = pcabi_internal::auxparse_headers(r->tags_device, r->tags_dev, (const uint8_t *)b->names.data(),
+                                                            b->name_off.data(), b->n, &b->aux, &b->aux_off)) {
+            delete b;
+            return rc;
+        }
+        b->as_stored.assign((size_t)b->n, 1);
+        b->tags_from_headers = true;
     }
     if (r->map) r->reader_at.store(r->pos, std::memory_order_relaxed);
     if (r->map) {
@@ -1307,6 +1324,16 @@ void pcabi_encode_dna5_gather(const uint64_t *src, const int64_t *len, const int
 int pcabi_fastx_keep_aux(pcabi_fastx *r, int on) {
     if (!r) return fail(PCABI_E_ARG, "bad arguments");
     if (r->bam) r->bam->keep_aux = on != 0;
+    return 0;
+}
+
+int pcabi_fastx_header_tags(pcabi_fastx *r, int on, int device) {
+    if (!r) return fail(PCABI_E_ARG, "bad arguments");
+    if (r->bam) return 0;   // a BAM reader's tags are its records' (pcabi_fastx_keep_aux)
+    if (r->raw) return fail(PCABI_E_ARG, "a raw reader keeps the file's text and parses no tags");
+    r->header_tags = on != 0;
+    r->tags_device = device;
+    if (r->header_tags && device >= 0 && !r->tags_dev) r->tags_dev = pcabi_internal::auxparse_dev_new();
     return 0;
 }
 
@@ -2260,6 +2287,8 @@ extern "C" int pcabi_reads_write_tags(const pcabi_reads *b, const char *path, in
             std::vector<uint8_t> &names = t_names[(size_t)t];
             for (int64_t i = b->n * t / nt; i < b->n * (t + 1) / nt; ++i)
                 read_parts(wa, i, rg, [&](const char *name, size_t nn, bool, int64_t s0, int64_t ns, int64_t q0, int64_t nq) {
+                    if (b->tags_from_headers)   // behind the first tab stand the tags the reader parsed
+                        if (const void *tab = std::memchr(name, '\t', nn)) nn = (size_t)((const char *)tab - name);
                     const pcabi_bam_part &bp = tp.parts[(size_t)k];
                     pcabi_fastx_part &p = fparts[(size_t)k++];
                     std::memset(&p, 0, sizeof p);

@@ -1065,3 +1065,63 @@ def fastx_pack(seq, qual, side, parts, out, fasta=False, device=0):
                                      arrs[2].size, _ptr(parts), parts.size, int(bool(fasta)), _ptr(out), out.size)
     check(int(rc), 'pcabi_fastx_pack_host')
     return out
+
+
+# ---- SAM tags read from FASTQ / FASTA headers (csrc/pcabi_auxparse.h, csrc/pcabi_auxparse.hip) ---------
+# include/pcabi.h pcabi_auxparse_part
+AUXPARSE_PART = np.dtype([('text_off', np.int64), ('out', np.int64), ('len', np.int64), ('text_len', np.int64),
+                          ('n_float', np.int32), ('tags', np.int32), ('left_out', np.int32), ('reserved', np.int32)])
+assert AUXPARSE_PART.itemsize == 48
+
+
+def auxparse_plan(text, parts, device=0):
+    """The length of every header's chain of aux bytes (pcabi_auxparse_plan): on GPU `device`, or with
+    the host build of the same rule when device < 0. text: the bytes the C-contiguous AUXPARSE_PART
+    array `parts` indexes (text_off / text_len set); 'len', 'n_float', 'tags' and 'left_out' are filled
+    in place. Adds the tags and the left-out fields to auxparse_counts(). Returns parts."""
+    text = _bytes_arg(text)
+    if parts.dtype != AUXPARSE_PART or not parts.flags['C_CONTIGUOUS']:
+        raise ValueError('auxparse_plan: parts is a C-contiguous AUXPARSE_PART array')
+    rc = lib().pcabi_auxparse_plan(int(device), _ptr(text), text.size, _ptr(parts), parts.size)
+    check(int(rc), 'pcabi_auxparse_plan')
+    return parts
+
+
+def auxparse_write(text, parts, out, device=0):
+    """Every header's chain written to out[part.out, part.out + part.len) (pcabi_auxparse_write): parts
+    as auxparse_plan left them, with 'out' set; out: a C-contiguous uint8 array, filled in place (bytes
+    no part owns keep their values) and returned."""
+    text = _bytes_arg(text)
+    parts = np.ascontiguousarray(parts, AUXPARSE_PART)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError('auxparse_write: out is a C-contiguous uint8 array')
+    rc = lib().pcabi_auxparse_write(int(device), _ptr(text), text.size, _ptr(parts), parts.size, _ptr(out), out.size)
+    check(int(rc), 'pcabi_auxparse_write')
+    return out
+
+
+def auxparse_counts(reset=False):
+    """(tags read, fields left out) since the last reset (pcabi_auxparse_counts)."""
+    v = np.zeros(2, np.int64)
+    lib().pcabi_auxparse_counts(int(bool(reset)), _ptr(v[0:1]), _ptr(v[1:2]))
+    return int(v[0]), int(v[1])
+
+
+def aux_parse(headers, device=None):
+    """The chain of BAM aux bytes of each header (bytes: the text after '@' / '>', or a single header
+    instead of a list): the tab-separated TG:T:value fields behind the first tab, b'' for a header
+    without tags. device None or < 0: the host build."""
+    if isinstance(headers, (bytes, bytearray)):
+        return aux_parse([headers], device)[0]
+    dev = -1 if device is None else int(device)
+    heads = [bytes(h) for h in headers]
+    parts = np.zeros(len(heads), AUXPARSE_PART)
+    parts['text_len'] = [len(h) for h in heads]
+    parts['text_off'][1:] = np.cumsum(parts['text_len'][:-1], dtype=np.int64)
+    blob = b''.join(heads)
+    auxparse_plan(blob, parts, dev)
+    parts['out'][1:] = np.cumsum(parts['len'][:-1], dtype=np.int64)
+    out = np.zeros(int(parts['len'].sum()), np.uint8)
+    auxparse_write(blob, parts, out, dev)
+    buf = out.tobytes()
+    return [buf[int(p['out']):int(p['out']) + int(p['len'])] for p in parts]

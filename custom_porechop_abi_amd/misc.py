@@ -57,6 +57,7 @@ def _declare(L):
         'pcabi_reads_write_bam_tags': ([P, ctypes.c_char_p, c_int, P, P, P, P, c_int, c_int, c_int, P, ctypes.c_char_p,
                                         i64, c_int, c_int, c_int], c_int),
         'pcabi_fastx_keep_aux': ([P, c_int], c_int),
+        'pcabi_fastx_header_tags': ([P, c_int, c_int], c_int),
         'pcabi_reads_aux': ([P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P)], c_int),
         'pcabi_fastx_bam_header': ([P, ctypes.POINTER(P), ctypes.POINTER(i64)], c_int),
         'pcabi_fastx_record_start': ([P, i64], i64),
@@ -106,7 +107,8 @@ class ReadBatch(object):
     bam_header: the header text (bytes) of the BAM file the batch came from, else None. With
     keep_aux (read_batches / load_batch) a BAM batch also holds its records' aux tags: aux_bytes /
     aux_off int64 [n + 1] and as_stored uint8 [n] (0: a reverse-strand record, whose bases the reader
-    reverse-complemented); all None otherwise."""
+    reverse-complemented); all None otherwise. A FASTA / FASTQ batch read with tags_from_headers holds the
+    tags parsed from its headers in the same three arrays (as_stored is 1 for every read)."""
 
     def __init__(self, handle, bam_header=None):
         L = _declare(lib())
@@ -290,10 +292,18 @@ def _check_gunzip_plain(gunzip_device, gunzip_plain):
         raise ValueError('gunzip_plain needs gunzip_device')
 
 
-def _fastx_open(L, path, raw, gunzip_device, keep_aux=False, gunzip_plain=False):
+def _check_tags_from_headers(tags_from_headers, keep_aux, raw):
+    if tags_from_headers and not keep_aux:
+        raise ValueError('tags_from_headers needs keep_aux')
+    if tags_from_headers and raw:
+        raise ValueError('tags_from_headers does not go with raw: a raw batch keeps the file\'s text')
+
+
+def _fastx_open(L, path, raw, gunzip_device, keep_aux=False, gunzip_plain=False, tags_from_headers=False, tags_device=None):
     """pcabi_fastx_open, or pcabi_fastx_open_dev when gunzip_device names a GPU (a block-gzipped file
     is then inflated there; any other file reads as before, unless gunzip_plain sends ordinary gzip
-    there too: pcabi_fastx_open_dev2). keep_aux: pcabi_fastx_keep_aux. Returns (rc, handle)."""
+    there too: pcabi_fastx_open_dev2). keep_aux: pcabi_fastx_keep_aux. tags_from_headers:
+    pcabi_fastx_header_tags on tags_device (None: the host build). Returns (rc, handle)."""
     h = ctypes.c_void_p()
     if gunzip_device is None:
         rc = L.pcabi_fastx_open(os.fsencode(path), int(raw), ctypes.byref(h))
@@ -303,6 +313,10 @@ def _fastx_open(L, path, raw, gunzip_device, keep_aux=False, gunzip_plain=False)
         rc = L.pcabi_fastx_open_dev(os.fsencode(path), int(raw), int(gunzip_device), ctypes.byref(h))
     if rc == 0 and keep_aux:
         L.pcabi_fastx_keep_aux(h, 1)
+    if rc == 0 and tags_from_headers:
+        rc = L.pcabi_fastx_header_tags(h, 1, -1 if tags_device is None else int(tags_device))
+        if rc != 0:
+            L.pcabi_fastx_close(h)
     return rc, h
 
 
@@ -327,7 +341,7 @@ def ramp_sizes(max_reads, remaining_reads=None, done=0):
 
 
 def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_range=None, first_reads=None,
-                 ramp=False, gunzip_device=None, keep_aux=False, gunzip_plain=False):
+                 ramp=False, gunzip_device=None, keep_aux=False, gunzip_plain=False, tags_from_headers=False):
     """Stream a FASTA / FASTQ(.gz) or unaligned BAM file as ReadBatch objects (pcabi_fastx_next; a BAM
     file's records arrive as FASTQ batches, see include/pcabi.h "unaligned BAM input"); byte_range =
     (begin, end) record starts of a plain file (record_boundaries) reads only that range;
@@ -339,11 +353,17 @@ def read_batches(path, max_reads=100000, max_bases=1 << 30, raw=False, byte_rang
     input with zlib; gunzip_plain (with gunzip_device): ordinary gzip, which has no index, is inflated
     there too, in parallel from speculative block starts (include/pcabi.h pcabi_gunzip_stream_*).
     keep_aux: a BAM input's batches keep their records' aux tags (ReadBatch.aux),
-    for write_reads(..., 'bam', keep_aux=True); any other input: no effect. A BAM input's batches
-    carry its header text (ReadBatch.bam_header)."""
+    for write_reads(..., 'bam', keep_aux=True); any other input: no effect, unless tags_from_headers
+    (with keep_aux) asks for the tags a FASTA / FASTQ input carries in its headers, as `samtools fastq -T`,
+    `dorado --emit-fastq` and write_reads(header_tags=True) write them: the tab-separated TG:T:value
+    fields of every header are parsed into aux bytes (include/pcabi.h "SAM tags read from FASTQ / FASTA
+    headers"), on gunzip_device when given, else with the host build, and the batch is written like one
+    read from BAM (engine.auxparse_counts() tells how many tags were read
+    and how many fields left out). A BAM input's batches carry its header text (ReadBatch.bam_header)."""
     _check_gunzip_plain(gunzip_device, gunzip_plain)
+    _check_tags_from_headers(tags_from_headers, keep_aux, raw)
     L = _declare(lib())
-    rc, h = _fastx_open(L, path, raw, gunzip_device, keep_aux, gunzip_plain)
+    rc, h = _fastx_open(L, path, raw, gunzip_device, keep_aux, gunzip_plain, tags_from_headers, gunzip_device)
     if rc != 0:
         raise ValueError(_open_error(path))
     if byte_range is not None and L.pcabi_fastx_set_range(h, int(byte_range[0]), int(byte_range[1])) != 0:
@@ -400,18 +420,20 @@ def text_chunks(path, chunk_bytes, gunzip_device=None, gunzip_plain=False):
         L.pcabi_fastx_close(h)
 
 
-def load_batch(path, raw=False, gunzip_device=None, keep_aux=False, gunzip_plain=False):
+def load_batch(path, raw=False, gunzip_device=None, keep_aux=False, gunzip_plain=False, tags_from_headers=False):
     """The whole FASTA, FASTQ or BAM file as one ReadBatch (pcabi_fastx_load); raw keeps the file's
     own text. gunzip_device: a GPU that inflates a block-gzipped (BGZF) input, a BAM file included,
-    whose records are then unpacked there too (pcabi_fastx_open_dev). keep_aux, gunzip_plain: as in
-    read_batches."""
+    whose records are then unpacked there too (pcabi_fastx_open_dev). keep_aux, gunzip_plain,
+    tags_from_headers: as in read_batches."""
     _check_gunzip_plain(gunzip_device, gunzip_plain)
+    _check_tags_from_headers(tags_from_headers, keep_aux, raw)
     L = _declare(lib())
     b = ctypes.c_void_p()
     bam = is_bam(path)
     plain = bool(gunzip_plain) and not bam and get_compression_type(path) == 'gz' and not _starts_bgzf(path)
-    if bam or plain or (gunzip_device is not None and _starts_bgzf(path)):
-        rc, h = _fastx_open(L, path, raw, gunzip_device if (plain or _starts_bgzf(path)) else None, keep_aux, plain)
+    if bam or plain or tags_from_headers or (gunzip_device is not None and _starts_bgzf(path)):
+        rc, h = _fastx_open(L, path, raw, gunzip_device if (plain or _starts_bgzf(path)) else None, keep_aux, plain,
+                            tags_from_headers, gunzip_device)
         if rc != 0:
             raise ValueError(_open_error(path))
         try:
@@ -578,7 +600,9 @@ def write_reads(batch, path, out_format='fastq', start_trim=None, end_trim=None,
     keep_aux / keep_mods / keep_moves, which are accepted for a text format only together with it. A
     '.gz' format with gzip_device lays the text out and compresses it on that GPU; every other case
     builds it on the host; both give the same decompressed bytes. A batch without aux bytes writes what
-    it writes without header_tags. engine.auxtext_counts() tells how many tags were written and how
+    it writes without header_tags. A batch whose tags were read from its own headers (read_batches
+    tags_from_headers) is written with the header up to its first tab as the name, so the tag text it
+    came with is not repeated in front of the new. engine.auxtext_counts() tells how many tags were written and how
     many were left out (a name outside [A-Za-z][A-Za-z0-9], an A / Z / H value with a byte outside
     0x20..0x7E).
     middle_cuts: per read a list of (begin, end) ranges of the trimmed sequence (the reference's

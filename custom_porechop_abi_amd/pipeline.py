@@ -73,6 +73,7 @@ class FileTrimmer(object):
     keep_mods = False                     # with keep_tags: MM ML MN of changed reads are dropped, not remapped
     keep_moves = False                    # with keep_tags: mv of changed reads is dropped, ts copied
     header_tags = False                   # with keep_tags: text outputs carry no tags in their headers
+    tags_from_headers = False             # with keep_tags: a text input's headers are not parsed for tags
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
@@ -80,8 +81,14 @@ class FileTrimmer(object):
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
-                 keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False):
+                 keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False, tags_from_headers=False):
         self.L = L = lib()
+        # tags_from_headers: a FASTA / FASTQ input's tags are read from its headers (misc.read_batches
+        # tags_from_headers; on the device with gunzip_on_device, else the host build), so every writer,
+        # the bins' included, carries them as it carries a BAM input's
+        if tags_from_headers and not keep_tags:
+            raise ValueError('tags_from_headers needs keep_tags')
+        self.tags_from_headers = bool(tags_from_headers)
         # header_tags: a text output format carries each part's tags in its header as SAM text
         # (misc.write_reads header_tags), the bins' writers included; gzip_on_device lays the text out on
         # the device
@@ -348,11 +355,11 @@ class FileTrimmer(object):
             for f, alb in files:
                 # batch sizes ramp up at the start and down at the end (misc.ramp_sizes): the first
                 # parse and the last write are small, so they overlap the other stages
+                keep = bool(getattr(self, 'keep_tags', False)) and (out_format == 'bam' or bool(getattr(self, 'header_tags', False)))
                 for b in misc.read_batches(f, max_reads=max_reads, byte_range=byte_range, ramp=True,
-                                           gunzip_device=getattr(self, 'gunzip_device', None),
-                                           keep_aux=bool(getattr(self, 'keep_tags', False)) and
-                                           (out_format == 'bam' or bool(getattr(self, 'header_tags', False))),
-                                           gunzip_plain=bool(getattr(self, 'gunzip_plain', False))):
+                                           gunzip_device=getattr(self, 'gunzip_device', None), keep_aux=keep,
+                                           gunzip_plain=bool(getattr(self, 'gunzip_plain', False)),
+                                           tags_from_headers=keep and bool(getattr(self, 'tags_from_headers', False))):
                     yield b, alb
                 if getattr(self, 'gunzip_plain', False):
                     # the reader thread's own figures (engine.gunzip_stream_stats is per thread)

@@ -957,7 +957,7 @@ void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
  *       ts are remapped by pcabi_reads_write_bam_tags ("move tables" below), here mv is dropped.
  *   pcabi_fastx_keep_aux : before the first pcabi_fastx_next, on = 1 makes a BAM reader keep every
  *       kept record's aux bytes and whether its bases are stored as written (not reverse-strand); any
- *       other input: no effect. A record whose aux chain does not walk (types A c C s S i I f Z H B)
+ *       other input: no effect (pcabi_fastx_header_tags fills a FASTA / FASTQ batch's). A record whose aux chain does not walk (types A c C s S i I f Z H B)
  *       is then PCABI_E_PARSE, raised after the records before it.
  *   pcabi_reads_aux : a batch's aux bytes: read i's are aux[aux_off[i], aux_off[i + 1]); as_stored[i].
  *       All three NULL when the batch holds none.
@@ -1085,7 +1085,7 @@ void pcabi_mods_last_times(int reset, double *ms, int64_t *bytes);
  * parts of a read that is not usable get no tag bytes (length 0). A table of more than INT32_MAX - 64
  * values is refused (no BAM record holds one).
  * Out of scope: direct-RNA files, whose move tables run against the sequence without the record saying
- * so; the sp and pi tags of split reads; tags in FASTQ header comments. ns (the sample count before
+ * so; the sp and pi tags of split reads. ns (the sample count before
  * trimming) does not depend on the position and stays with the other tags.
  *   pcabi_moves_read : one read with an mv tag: mv_off = the first value of the array (the stride) in
  *       the tag blob, n_vals = how many values (stride included), ts < 0 = no ts tag; its parts are
@@ -1195,15 +1195,16 @@ int pcabi_reads_write_bam_tags(const pcabi_reads *b, const char *path, int appen
  *   pcabi_reads_write_tags : pcabi_reads_write_dev with keep_aux (1, 2), tag_flags
  *       (PCABI_BAM_KEEP_MOVES) and header_tags. header_tags == 0, keep_aux == 0 or a batch without aux
  *       bytes: exactly pcabi_reads_write_dev. Else every record's header is the name as the text writers
- *       write it followed by the SAM text above of the part's aux bytes. gz = 0 / 1: the host build
+ *       write it (for a batch whose tags were parsed from its headers, pcabi_fastx_header_tags: up to
+ *       its first tab) followed by the SAM text above of the part's aux bytes. gz = 0 / 1: the host build
  *       builds the text. gz = 2 / 3: on device gzip_device (-1: the current device) the remapped tags
  *       are sized and written into the device copy of the side blob as for BAM output, k_auxtext_size
  *       gives every part's text length, the host plans the records' offsets and the line-aligned
  *       deflate blocks (pcabi_gzip_plan_lines' rules) from the line lengths alone, k_fastx_pack lays the
  *       text out in device memory and the gzip / BGZF encoder compresses it there; only compressed
  *       bytes come back. Both paths decompress to the same bytes.
- * Out of scope: reading tags back from header comments; the sp / pi tags of split reads; direct-RNA
- * move tables; escaping the tags that are left out.
+ * Out of scope: the sp / pi tags of split reads; direct-RNA move tables; escaping the tags that are
+ * left out.
  */
 #define PCABI_FASTX_RNA 1 /* pcabi_fastx_part flags: T is written as U */
 typedef struct pcabi_auxtext_part {
@@ -1242,6 +1243,81 @@ int pcabi_reads_write_tags(const pcabi_reads *b, const char *path, int append, i
                            const int32_t *start_trim, const int32_t *end_trim, const int64_t *cut_off,
                            const int64_t *cuts, int min_split_read_size, int discard_middle, int untrimmed,
                            const uint8_t *select, int gzip_device, int keep_aux, int tag_flags, int header_tags);
+
+/* ---- SAM tags read from FASTQ / FASTA headers (csrc/pcabi_auxparse.h, csrc/pcabi_auxparse.hip) ----
+ * The other direction: a FASTQ / FASTA file whose headers carry tags as `dorado --emit-fastq`,
+ * `samtools fastq -T` and pcabi_reads_write_tags write them. A reader with pcabi_fastx_header_tags parses
+ * every header into a chain of BAM aux bytes and puts it where a BAM reader puts a record's
+ * (pcabi_reads_aux, as_stored = 1 for every read), so the writers remap MM ML MN mv ts onto trimmed
+ * reads and split pieces exactly as for BAM input.
+ * The rule. The header is the text after '@' / '>', without the line end. It is split at tabs only.
+ * Field 0 is the name and any blank-separated comment; it holds no tags. Every later field is a
+ * candidate: a well-formed one appends one tag to the chain, in header order (duplicate names are
+ * kept); any other -- an empty field between two tabs or after a trailing tab included -- is left out
+ * and counted. A header without a tab gives an empty chain and counts nothing. A candidate is TG:T:V
+ * with TG matching [A-Za-z][A-Za-z0-9], and by type T:
+ *   A   V exactly one byte 0x20..0x7E                          -> TG A byte
+ *   i   V [-+]?[0-9]{1,10} with a value in -2^31 .. 2^32 - 1   -> htslib's smallest type: a leading '-'
+ *       selects signed (c >= -128, s >= -32768, else i), otherwise C <= 255, S <= 65535, else I; "-0"
+ *       is c 0
+ *   f   V SAM's float syntax [-+]?[0-9]*\.?[0-9]+([eE][-+]?[0-9]+)? or [-+]?inf or [-+]?nan, at most
+ *       31 bytes                                               -> TG f and the float32 of C's (float)strtod(V)
+ *   Z   V any bytes 0x20..0x7E, may be empty                   -> TG Z V NUL
+ *   H   V an even number of hex digits, either case            -> TG H V NUL
+ *   B   V a subtype letter of cCsSiIf, then zero or more ",element"; an integer element is
+ *       [-+]?[0-9]{1,10} inside the subtype's range, a float element as f
+ *                                                              -> TG B subtype, the count as u32 LE, the elements LE
+ * One bad element leaves the whole field out. Nothing is escaped or repaired.
+ * Floats are the host's, as in the writer: the device checks a float's syntax (the field's length
+ * depends on it) and leaves a fix-up -- where the text lies, how long it is, where the 4 bytes go; the
+ * host fills the fix-ups with strtod once the chains are back and never scans the text itself.
+ *   pcabi_auxparse_part : one header text[text_off, text_off + text_len); len = its chain's length, out =
+ *       where the chain goes, n_float = the f values and B:f elements in it, tags / left_out = the fields
+ *       read and left out.
+ *   pcabi_auxparse_plan  : fills parts[].len, n_float, tags and left_out and adds the last two to the
+ *       counters. device >= 0: the text and the table go up and k_auxparse_size walks one header per
+ *       wave; device < 0: the host build of the same rule (no GPU needed). A part outside the text is
+ *       refused (PCABI_E_ARG).
+ *   pcabi_auxparse_write : writes every part's chain to out[part.out, part.out + part.len). A len (or
+ *       a count) that is not what the plan gives, ranges that overlap or lie outside out[0, out_cap) are refused
+ *       (PCABI_E_ARG). device >= 0: k_auxparse_write stores the chains and the floats' fix-up records (a
+ *       part's first slot is the host's prefix sum over n_float); the output lies between 64 guard
+ *       bytes, checked after the kernel (PCABI_E_DEVICE if it wrote outside). Bytes no part owns keep
+ *       their values.
+ *   pcabi_auxparse_counts : tags read and fields left out, as pcabi_auxparse_plan and a reader with
+ *       pcabi_fastx_header_tags counted them since the last call with reset != 0.
+ *   pcabi_auxparse_last_times : on != 0 makes the device paths time their kernels with device events;
+ *       ms[0..1] = milliseconds of k_auxparse_size and k_auxparse_write, bytes[0..1] = what they read and
+ *       wrote, since the last call with reset != 0.
+ *   pcabi_fastx_header_tags : before the first pcabi_fastx_next, on != 0 makes a FASTA / FASTQ reader
+ *       fill every batch's aux bytes from its headers. device >= 0: the batch's header blob goes up once,
+ *       both kernels run on a stream of the reader's, and the chains and the fix-ups come back; device
+ *       < 0: the host build on the io threads. A BAM reader: no effect. A raw reader: PCABI_E_ARG. The
+ *       batch remembers that its tags came from its headers: pcabi_reads_write_tags then takes as a
+ *       record's name the header up to its first tab (the `_k` of a split piece in front of it, where it
+ *       goes today), so the tags that were parsed are not written a second time in front of the new
+ *       ones. Every other writer and every other batch is unchanged; the BAM writer's name ends at the
+ *       first blank or tab anyway.
+ * Out of scope: sharded runs (shards.py) and text_chunks; tags separated by blanks instead of tabs;
+ * carrying a left-out field or the free-text comment into BAM (CO); the sp / pi tags of split reads;
+ * direct-RNA move tables; keeping the chains on the device for the writer.
+ */
+typedef struct pcabi_auxparse_part {
+    int64_t text_off; /* the header in the text blob                      */
+    int64_t out;      /* where its chain goes                             */
+    int64_t len;      /* the chain's length (pcabi_auxparse_plan)         */
+    int64_t text_len; /* below 2^31                                       */
+    int32_t n_float;  /* f values and B:f elements of the chain (plan)    */
+    int32_t tags;     /* fields read (plan)                               */
+    int32_t left_out; /* fields left out (plan)                           */
+    int32_t reserved;
+} pcabi_auxparse_part;
+int pcabi_auxparse_plan(int device, const uint8_t *text, int64_t text_n, pcabi_auxparse_part *parts, int64_t n_parts);
+int pcabi_auxparse_write(int device, const uint8_t *text, int64_t text_n, const pcabi_auxparse_part *parts, int64_t n_parts,
+                         uint8_t *out, int64_t out_cap);
+void pcabi_auxparse_counts(int reset, int64_t *tags_read, int64_t *fields_left_out);
+void pcabi_auxparse_last_times(int on, int reset, double *ms, int64_t *bytes);
+int pcabi_fastx_header_tags(pcabi_fastx *r, int on, int device);
 
 #ifdef __cplusplus
 }
