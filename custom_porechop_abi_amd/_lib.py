@@ -186,6 +186,12 @@ def lib():
         'pcabi_auxparse_counts': ([c_int, c_p, c_p], None),
         'pcabi_auxparse_last_times': ([c_int, c_int, c_p, c_p], None),
         'pcabi_fastx_header_tags': ([c_p, c_int, c_int], c_int),
+        'pcabi_qual_seg_bound': ([c_p, c_i64], c_i64),
+        'pcabi_qual_scratch_bytes': ([c_i64, c_i64], c_i64),
+        'pcabi_qual_filter_dev': ([c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p], c_int),
+        'pcabi_qual_filter_host': ([c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p], c_int),
+        'pcabi_qual_error_table': ([c_p], None),
+        'pcabi_qual_last_times': ([c_int, c_int, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -235,7 +241,9 @@ def exported_symbols():
             'pcabi_fastx_open_dev2', 'pcabi_auxtext_plan', 'pcabi_auxtext_write', 'pcabi_auxtext_counts',
             'pcabi_auxtext_last_times', 'pcabi_fastx_pack_plan', 'pcabi_fastx_pack_dev', 'pcabi_fastx_pack_host',
             'pcabi_reads_write_tags', 'pcabi_auxparse_plan', 'pcabi_auxparse_write', 'pcabi_auxparse_counts',
-            'pcabi_auxparse_last_times', 'pcabi_fastx_header_tags']
+            'pcabi_auxparse_last_times', 'pcabi_fastx_header_tags', 'pcabi_qual_seg_bound',
+            'pcabi_qual_scratch_bytes', 'pcabi_qual_filter_dev', 'pcabi_qual_filter_host', 'pcabi_qual_error_table',
+            'pcabi_qual_last_times']
 
 
 class CrossRegion(ctypes.Structure):

@@ -1,5 +1,5 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_auxparse.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_auxparse.hip, pcabi_qual.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
 // the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
 // pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
 // compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).

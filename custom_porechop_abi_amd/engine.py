@@ -1125,3 +1125,58 @@ def aux_parse(headers, device=None):
     auxparse_write(blob, parts, out, dev)
     buf = out.tobytes()
     return [buf[int(p['out']):int(p['out']) + int(p['len'])] for p in parts]
+
+
+# ---- quality stage: end crop and read filter (csrc/pcabi_qual.h, csrc/pcabi_qual.hip) ---------------
+# include/pcabi.h pcabi_qual_read, pcabi_qual_opts
+QUAL_READ = np.dtype([('front', np.int32), ('tail', np.int32), ('kept', np.int32), ('flags', np.int32), ('q_sum', np.int64),
+                      ('err_sum', np.uint64)])
+QUAL_OPTS = np.dtype([('window', np.int32), ('reserved', np.int32), ('min_window_sum', np.int64), ('min_length', np.int64),
+                      ('max_length', np.int64), ('max_mean_err', np.uint64)])
+QUAL_TOO_SHORT, QUAL_TOO_LONG, QUAL_LOW_QUALITY, QUAL_NO_QUALITIES = 1, 2, 4, 8
+QUAL_FAIL = QUAL_TOO_SHORT | QUAL_TOO_LONG | QUAL_LOW_QUALITY
+assert QUAL_READ.itemsize == 32 and QUAL_OPTS.itemsize == 40
+
+
+def qual_error_table():
+    """E[q] = round(2^32 * 10^(-q / 10)) for q = 0..93 as the library holds it (pcabi_qual_error_table)."""
+    t = np.zeros(94, np.uint64)
+    lib().pcabi_qual_error_table(_ptr(t))
+    return t
+
+
+def qual_opts(window=0, min_window_q=0.0, min_length=0, max_length=0, min_mean_q=0.0):
+    """The thresholds as the integers the library takes (a QUAL_OPTS record): min_window_sum =
+    ceil(min_window_q * window); max_mean_err = floor(2^32 * 10^(-min_mean_q / 10)), the mean error
+    probability that mean quality stands for (min_mean_q <= 0: 2^32, no test). The only place where the
+    thresholds are converted."""
+    import math
+    o = np.zeros(1, QUAL_OPTS)
+    o['window'] = int(window)
+    o['min_window_sum'] = int(math.ceil(float(min_window_q) * int(window)))
+    o['min_length'], o['max_length'] = int(min_length), int(max_length)
+    o['max_mean_err'] = 1 << 32 if min_mean_q <= 0 else int(math.floor(2.0 ** 32 * 10.0 ** (-float(min_mean_q) / 10.0)))
+    return o
+
+
+def quality_filter(qual, span_off, span_len, window=0, min_window_q=0.0, min_length=0, max_length=0, min_mean_q=0.0, device=0,
+                   opts=None):
+    """Every read's span cropped at both ends to its outermost windows of `window` qualities whose mean
+    Phred is min_window_q or more, then its length and mean-quality tests (pcabi_qual_filter_host; the
+    rule: include/pcabi.h). qual: the quality bytes; span_off / span_len: every read's span in them,
+    span_off < 0 for a read without qualities. On GPU `device`, or with the host build of the same code
+    when device is None or < 0. opts: a QUAL_OPTS record that replaces the thresholds (the integers as
+    they are). Returns a QUAL_READ array: front, tail, kept, flags (QUAL_*), q_sum, err_sum."""
+    qual = _bytes_arg(qual)
+    span_off = np.ascontiguousarray(span_off, np.int64)
+    span_len = np.ascontiguousarray(span_len, np.int32)
+    if span_off.shape != span_len.shape or span_off.ndim != 1:
+        raise ValueError('quality_filter: span_off and span_len are one-dimensional and equally long')
+    if opts is None:
+        opts = qual_opts(window, min_window_q, min_length, max_length, min_mean_q)
+    opts = np.ascontiguousarray(opts, QUAL_OPTS)
+    out = np.zeros(span_off.size, QUAL_READ)
+    rc = lib().pcabi_qual_filter_host(-1 if device is None else int(device), _ptr(qual), qual.size, _ptr(span_off), _ptr(span_len),
+                                      span_off.size, _ptr(opts), _ptr(out))
+    check(int(rc), 'pcabi_qual_filter_host')
+    return out

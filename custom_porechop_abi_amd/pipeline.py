@@ -5,6 +5,7 @@
       -> H2D of the packed Dna5 codes, start / end window views        (engine layout, no repack)
       -> k_tile_windows / k_align cross products / k_end_trim           (find_adapters_at_read_ends)
       -> trims D2H (8 B / read)
+      -> opt-in: the quality stage crops the trimmed spans and tests the reads (pcabi_qual_filter_dev)
       -> pcabi_middle_scan_dev over the trimmed reads                   (find_adapters_in_read_middles)
       -> middle cut ranges (NanoporeRead._apply_middle_hit: pcabi_middle_cuts on the device)
       -> the fork's start-and-end filter (porechop_abi.py:36-39)
@@ -23,7 +24,8 @@ import numpy as np
 
 from . import misc
 from ._lib import check, cross_regions, lib
-from .engine import encode_adapters, middle_cuts
+from .engine import QUAL_FAIL, QUAL_LOW_QUALITY, QUAL_NO_QUALITIES, QUAL_READ, QUAL_TOO_LONG, QUAL_TOO_SHORT, encode_adapters, \
+    middle_cuts, qual_opts
 from .porechop_abi import middle_adapter_list
 
 VP = ctypes.c_void_p
@@ -39,6 +41,16 @@ def _bgzf_mode(trimmer, out_format):
 def _finish_mode(trimmer, out_format):
     """Whether the files of this run end with the BGZF end-of-file marker: BGZF text, or BAM."""
     return out_format == 'bam' or _bgzf_mode(trimmer, out_format)
+
+
+def _trimmed_span(lens, st, et):
+    """get_seq_with_start_end_adapters_trimmed (nanopore_read.py:66-71): the Python slice seq[st:len - et]
+    of the reference as (first base, length) per read; a read with st == et == 0 is taken whole."""
+    trimmed = (st > 0) | (et > 0)
+    end = lens - et
+    end = np.where(end < 0, np.maximum(lens + end, 0), end)
+    a = np.minimum(st, lens)
+    return np.where(trimmed, a, 0), np.where(trimmed, np.maximum(end - a, 0), lens)
 
 
 def _bam_kw(trimmer, out_format, b):
@@ -62,7 +74,22 @@ class FileTrimmer(object):
     Options follow the reference's arguments (arg_parser.py defaults): end_size 150,
     end_threshold 75, extra_end_trim 2, min_trim_size 4, middle_threshold 90, extra middle trim
     10 (good side) / 100 (bad side), min_split_read_size 1000, no_split False, discard_middle
-    False, adapter filter on (the fork's)."""
+    False, adapter filter on (the fork's).
+
+    The quality stage (off by default; on when quality_window, min_length, max_length or min_mean_q is
+    set) does on the device what NanoFilt, chopper or fastplong's --cut_front --cut_tail --mean_qual
+    --length_required do to the trimmed file (engine.quality_filter; the rule: include/pcabi.h). It runs
+    after the end trim and before the middle scan on the span the adapter trims left: quality_window /
+    quality_window_q crop the span at both ends to its outermost windows of quality_window bases with a
+    mean Phred of quality_window_q or more, and the crops are added to start_trim / end_trim, so every
+    writer, BAM with remapped MM ML MN mv ts included, writes the cropped read as it writes a trimmed
+    one; min_length / max_length / min_mean_q (the Phred of the mean error probability) then test the
+    kept span and clear the read's keep bit. A read without qualities is not cropped and passes the
+    quality test. The fork's start-and-end filter still goes by the adapter trims; with
+    filter_reads=False keep is the pass mask. The filter sees the kept span with its middle adapters:
+    split pieces are not filtered one by one. The barcode bins go through the same trims and keep mask;
+    with untrimmed=True their writer ignores the trims, as it does today, so the crop is not visible
+    there while the filter still applies. last_quality holds the last batch's QUAL_READ records."""
 
     barcode_dir = None                    # -b off (set by __init__)
     gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
@@ -74,6 +101,12 @@ class FileTrimmer(object):
     keep_moves = False                    # with keep_tags: mv of changed reads is dropped, ts copied
     header_tags = False                   # with keep_tags: text outputs carry no tags in their headers
     tags_from_headers = False             # with keep_tags: a text input's headers are not parsed for tags
+    quality_window = 0                    # no quality crop
+    quality_window_q = 0.0                # with quality_window: every window qualifies
+    min_length = 0                        # no read is too short
+    max_length = 0                        # no read is too long
+    min_mean_q = 0.0                      # no read is of too low a quality
+    last_quality = None                   # the quality stage's records of the last batch (stage on)
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
@@ -81,8 +114,13 @@ class FileTrimmer(object):
                  filter_reads=True, device=0, barcode_dir=None, forward_or_reverse_barcodes='forward',
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
-                 keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False, tags_from_headers=False):
+                 keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False, tags_from_headers=False, quality_window=0,
+                 quality_window_q=0.0, min_length=0, max_length=0, min_mean_q=0.0):
         self.L = L = lib()
+        if not 0 <= int(quality_window) <= 64:
+            raise ValueError('quality_window is 0 (off) or 1..64')
+        self.quality_window, self.quality_window_q = int(quality_window), float(quality_window_q)
+        self.min_length, self.max_length, self.min_mean_q = int(min_length), int(max_length), float(min_mean_q)
         # tags_from_headers: a FASTA / FASTQ input's tags are read from its headers (misc.read_batches
         # tags_from_headers; on the device with gunzip_on_device, else the host build), so every writer,
         # the bins' included, carries them as it carries a BAM input's
@@ -197,6 +235,36 @@ class FileTrimmer(object):
             check(self.L.pcabi_dev_copy_async(p, arr.ctypes.data_as(VP), arr.nbytes, 0, self.stream), 'h2d')
         return p
 
+    def _quality_on(self):
+        return self.quality_window > 0 or self.min_length > 0 or self.max_length > 0 or self.min_mean_q > 0
+
+    def _quality_stage(self, batch, lens, trims, d_qual):
+        """The quality stage on the spans the adapter trims left (the qualities are on their way to the
+        device): -> (start_trim, end_trim) with the crops added, and the reads' QUAL_READ records."""
+        L, nb = self.L, batch.n
+        st, et = trims[0].astype(np.int64), trims[1].astype(np.int64)
+        a, n = _trimmed_span(lens, st, et)
+        has_q = np.diff(batch.qual_off) == lens
+        span_off = np.where(has_q, batch.qual_off[:-1] + a, -1).astype(np.int64)
+        span_len = n.astype(np.int32)
+        opts = qual_opts(self.quality_window, self.quality_window_q, self.min_length, self.max_length, self.min_mean_q)
+        n_segs = int(L.pcabi_qual_seg_bound(span_len.ctypes.data_as(VP), nb))
+        need = int(L.pcabi_qual_scratch_bytes(nb, n_segs))
+        if need < 0:
+            check(need, 'pcabi_qual_scratch_bytes')
+        recs = np.zeros(nb, QUAL_READ)
+        d_off, d_len = self._h2d('qoff', span_off), self._h2d('qlen', span_len)
+        d_out, d_scr = self._buf('qout', recs.nbytes), self._buf('qscratch', need)
+        check(L.pcabi_qual_filter_dev(d_qual, batch.qual.size, d_off, d_len, nb, n_segs, opts.ctypes.data_as(VP), d_out, d_scr, need,
+                                      self.stream), 'pcabi_qual_filter_dev')
+        check(L.pcabi_dev_copy_async(recs.ctypes.data_as(VP), d_out, recs.nbytes, 1, self.stream), 'd2h')
+        check(L.pcabi_stream_sync(self.stream), 'sync')
+        front, tail = recs['front'].astype(np.int64), recs['tail'].astype(np.int64)
+        cropped = front + tail > 0
+        new_st = np.where(cropped, a + front, st).astype(np.int32)
+        new_et = np.where(cropped, lens - (a + n - tail), et).astype(np.int32)
+        return new_st, new_et, recs
+
     def _tick(self, key, t):
         now = time.perf_counter()
         self.times[key] = self.times.get(key, 0.0) + now - t
@@ -219,6 +287,10 @@ class FileTrimmer(object):
             e_start = np.minimum(-E, lens)
         e_len = (lens - e_start).astype(np.int32)
         d_codes = self._h2d('codes', batch.codes)
+        quality = self._quality_on()
+        # the qualities cross PCIe beside the alignment
+        d_qual = self._h2d('qual', batch.qual) if quality and nb else None
+        self.last_quality = np.zeros(0, QUAL_READ) if quality else None
         trims = np.zeros((2, nb), np.int32)
         res = [None, None]
         regions = []
@@ -262,19 +334,39 @@ class FileTrimmer(object):
         elif self.barcode_dir is not None:
             self.last_calls = np.full(nb, -1, np.int32)
         t = self._tick('end_trim', t)
+        adapter_trims = trims
+        if quality and nb:
+            # before the middle scan forms its windows: middle cuts are positions of the trimmed sequence
+            st, et, self.last_quality = self._quality_stage(batch, lens, trims, d_qual)
+            trims = (st, et)
+            t = self._tick('quality', t)
+        cut_off, cuts, hits = self.middle_scan(batch, trims[0], trims[1], d_codes)
+        t = self._tick('middle', t)
+        keep = None
+        if self.filter_reads:
+            # the fork's filter: start AND end alignments (a recorded alignment always trims >= 1)
+            keep = ((adapter_trims[0] > 0) & (adapter_trims[1] > 0)).astype(np.uint8)
+        if quality:
+            passed = ((self.last_quality['flags'] & QUAL_FAIL) == 0).astype(np.uint8)
+            keep = passed if keep is None else keep & passed
+        return trims[0], trims[1], cut_off, cuts, hits, keep
+
+    def middle_scan(self, batch, start_trim, end_trim, d_codes=None):
+        """The middle adapters of the reads as start_trim / end_trim leave them: (cut_off, cuts, hits).
+        d_codes: the batch's codes on the device (trim() passes its copy), else they are uploaded."""
+        L, sc, nb = self.L, self.sc, batch.n
+        lens = batch.lengths.astype(np.int64)
         cut_off = np.zeros(nb + 1, np.int64)
         cuts = np.zeros(0, np.int64)
         hits = np.zeros((6, 0), np.int32)
         if self.mid_adps and not self.no_split and nb:
+            if d_codes is None:
+                d_codes = self._h2d('codes', batch.codes)
             # get_seq_with_start_end_adapters_trimmed (nanopore_read.py:66-71): the Python slice
             # seq[st:len - et] of the reference, as a window of the packed read
-            st, et = trims[0].astype(np.int64), trims[1].astype(np.int64)
-            trimmed = (st > 0) | (et > 0)
-            end = lens - et
-            end = np.where(end < 0, np.maximum(lens + end, 0), end)
-            a = np.minimum(st, lens)
-            t_len = np.where(trimmed, np.maximum(end - a, 0), lens).astype(np.int32)
-            t_off = batch.code_off + np.where(trimmed, a, 0)
+            a, t_len = _trimmed_span(lens, np.asarray(start_trim, np.int64), np.asarray(end_trim, np.int64))
+            t_len = t_len.astype(np.int32)
+            t_off = batch.code_off + a
             d_toff, d_tlen = self._h2d('toffm', t_off), self._h2d('tlenm', t_len)
             cap = max(4096, nb)
             while True:
@@ -291,12 +383,7 @@ class FileTrimmer(object):
             # NanoporeRead._apply_middle_hit's trim ranges (nanopore_read.py:242-250) on the device,
             # grouped per read in the writer's cut layout
             cut_off, cuts = middle_cuts(hits, nb, self.bad_start, self.bad_end, self.good, self.bad, self.device)
-        t = self._tick('middle', t)
-        keep = None
-        if self.filter_reads:
-            # the fork's filter: start AND end alignments (a recorded alignment always trims >= 1)
-            keep = ((trims[0] > 0) & (trims[1] > 0)).astype(np.uint8)
-        return trims[0], trims[1], cut_off, cuts, hits, keep
+        return cut_off, cuts, hits
 
     def albacore_filter(self, calls, albacore):
         """determine_barcode's Albacore cross-check (nanopore_read.py:479-482): a read binned by
@@ -322,8 +409,15 @@ class FileTrimmer(object):
         Three stages overlap across batches: a reader thread parses the next batch, this thread
         runs the device work, a writer thread writes the previous batch (in file order). The
         library's parse, alignment and write calls release the GIL. times: 'parse' / 'write_wait'
-        are this thread's waits, 'read' / 'write' the reader's / writer's own busy time (overlapped)."""
+        are this thread's waits, 'read' / 'write' the reader's / writer's own busy time (overlapped).
+
+        With the quality stage on, counts['quality'] tallies its records: cropped_reads, cropped_bases,
+        too_short, too_long, low_quality, no_qualities."""
         counts = {'reads_in': 0, 'reads_kept': 0}
+        quality = None
+        if getattr(self, '_quality_on', lambda: False)():
+            quality = counts['quality'] = {k: 0 for k in ('cropped_reads', 'cropped_bases', 'too_short', 'too_long', 'low_quality',
+                                                         'no_qualities')}
         # PCABI_PIPE_TRACE=1: (stage, batch, begin, end) per stage and batch in self.trace (the
         # pipeline's timeline: which stage holds the others up)
         trace = self.trace = [] if os.environ.get('PCABI_PIPE_TRACE') == '1' else None
@@ -444,6 +538,14 @@ class FileTrimmer(object):
                 t0 = t
                 st, et, co, cu, _, keep = self.trim(b) if alb is None else self.trim(b, albacore=alb)
                 calls = self.last_calls if self.barcode_dir is not None else None
+                if quality is not None:
+                    q = self.last_quality
+                    crop = q['front'].astype(np.int64) + q['tail']
+                    quality['cropped_reads'] += int((crop > 0).sum())
+                    quality['cropped_bases'] += int(crop.sum())
+                    for key, bit in (('too_short', QUAL_TOO_SHORT), ('too_long', QUAL_TOO_LONG), ('low_quality', QUAL_LOW_QUALITY),
+                                     ('no_qualities', QUAL_NO_QUALITIES)):
+                        quality[key] += int(((q['flags'] & bit) != 0).sum())
                 t1 = time.perf_counter()
                 wq.put((k, b, st, et, co, cu, keep, calls))   # the writer drains even after a failure
                 del b

@@ -1319,6 +1319,89 @@ void pcabi_auxparse_counts(int reset, int64_t *tags_read, int64_t *fields_left_o
 void pcabi_auxparse_last_times(int on, int reset, double *ms, int64_t *bytes);
 int pcabi_fastx_header_tags(pcabi_fastx *r, int on, int device);
 
+/* ---- quality stage: end crop and read filter (csrc/pcabi_qual.h, csrc/pcabi_qual.hip) -----------
+ * What the quality filter that follows an adapter trimmer does, on the spans the end trim left: each
+ * span is cropped at both ends to its outermost windows of acceptable quality, then the read passes or
+ * fails length and mean-quality limits. The caller turns front / tail into trims and the pass bits into
+ * its keep mask (pipeline.FileTrimmer), so every writer remaps MM ML MN mv ts for the cropped read as
+ * it does for a trimmed one.
+ * Qualities. A quality byte c is Phred q = clamp(c - 33, 0, 93): bytes below 33 give 0, above 126 give
+ * 93. A read whose quality length differs from its sequence length (FASTA, a BAM record without
+ * qualities, a '+'-padded record) is without qualities: the caller passes span_off < 0; it is never
+ * cropped and passes the quality test, its length tests apply.
+ * The span of read i is the n = span_len[i] bytes qual[span_off[i], span_off[i] + n).
+ * The crop. window W (1..64; 0: no crop) and min_window_sum: with S(p) the sum of q over [p, p + W), f
+ * the least and g the greatest p in [0, n - W] with S(p) >= min_window_sum, the kept span is
+ * [f, g + W): front = f, tail = n - (g + W), kept = g + W - f. No such window, or n < W: front = n,
+ * tail = 0, kept = 0.
+ * Trims handed on, for a span [a, a + n) of a read of ns bases (a, n from the writers' slice of the
+ * adapter trims, pcabi_reads_write): only when front + tail > 0, start_trim' = a + front and
+ * end_trim' = ns - (a + n - tail); these are in range, so the writers' slice gives exactly the kept
+ * span. Otherwise both trims stay as they are.
+ * Sums over the kept span: q_sum = the sum of q; err_sum = the sum of E[q], E[q] = round(2^32 *
+ * 10^(-q / 10)) for q = 0..93, 94 constants (pcabi_qual_error_table). A batch holds at most 2^31 bytes,
+ * so err_sum stays below 2^63.
+ * Flags: PCABI_QUAL_TOO_SHORT kept < min_length; PCABI_QUAL_TOO_LONG max_length > 0 and kept >
+ * max_length; PCABI_QUAL_LOW_QUALITY the read has qualities and err_sum > kept * max_mean_err
+ * (max_mean_err in [0, 2^32]; 2^32 switches the test off: the mean of the error probabilities, as ONT
+ * tools and dorado's qs tag take it); PCABI_QUAL_NO_QUALITIES informational. A read passes when none of
+ * the first three is set. Equality passes: a window sum equal to min_window_sum qualifies, err_sum
+ * equal to kept * max_mean_err is not LOW_QUALITY.
+ *   pcabi_qual_seg_bound     : (host) the segments (4096 bytes each) the uncropped spans would take: the
+ *       upper bound pcabi_qual_filter_dev's grid is sized by.
+ *   pcabi_qual_scratch_bytes : the scratch pcabi_qual_filter_dev needs for n_reads and that bound.
+ *   pcabi_qual_filter_dev    : device pointers on the current device, asynchronous on `stream`; nothing
+ *       comes back to the host in between. k_qual_crop, one wave per read, takes 64 window starts a pass
+ *       from the front (a wave prefix sum gives the 64 window sums, a ballot the first that qualifies)
+ *       and stops at the first pass that holds one, then the same from the tail; a device scan of the
+ *       kept spans' segment counts gives every read's first segment; k_qual_sum, one wave per segment,
+ *       takes 16-byte loads masked to the segment at both ends (no byte outside a kept span is read)
+ *       with E[] in LDS; k_qual_finish adds a read's segments and sets its flags. out[i] is complete
+ *       when the stream has run. A span that does not lie inside the blob is treated as a read without
+ *       qualities (nothing of it is read). window > 64, max_mean_err > 2^32, a blob over 2^31 bytes or a
+ *       scratch buffer that is too small are refused (PCABI_E_ARG) before any launch.
+ *   pcabi_qual_filter_host   : host buffers, uploaded and run as above on `device`; device < 0 runs the
+ *       host build of the same header on the io threads (no GPU needed). A span outside the blob is
+ *       refused as well (PCABI_E_ARG), before any launch.
+ *   pcabi_qual_error_table   : E[0..93].
+ *   pcabi_qual_last_times    : on != 0 makes pcabi_qual_filter_host time its kernels with device events;
+ *       ms[0..3] = milliseconds of k_qual_crop, of k_qual_sum, the wall time of the host build and the
+ *       wall time of the device stage behind the uploads (kernels, scan, records back); bytes[0..1] =
+ *       the spans' bytes the two kernels were given; all since the last call with reset != 0.
+ * Out of scope: per-piece filtering of split reads (the filter sees the kept span, middle adapters
+ * included); rewriting dorado's qs tag for a cropped read; fastp's base-by-base trim inside the first
+ * good window; windows over 64; sharded runs; qualities kept on the device by the BAM or gunzip readers.
+ */
+#define PCABI_QUAL_TOO_SHORT 1
+#define PCABI_QUAL_TOO_LONG 2
+#define PCABI_QUAL_LOW_QUALITY 4
+#define PCABI_QUAL_NO_QUALITIES 8
+typedef struct pcabi_qual_opts {
+    int32_t window; /* W: 1..64, 0 = no crop */
+    int32_t reserved;
+    int64_t min_window_sum;
+    int64_t min_length;
+    int64_t max_length;    /* 0 = no limit */
+    uint64_t max_mean_err; /* units of 2^-32; 2^32 = no test */
+} pcabi_qual_opts;
+typedef struct pcabi_qual_read {
+    int32_t front, tail; /* bytes cropped from the span's two ends */
+    int32_t kept;
+    int32_t flags;       /* PCABI_QUAL_* */
+    int64_t q_sum;
+    uint64_t err_sum;
+} pcabi_qual_read;
+int64_t pcabi_qual_seg_bound(const int32_t *span_len, int64_t n_reads);
+int64_t pcabi_qual_scratch_bytes(int64_t n_reads, int64_t n_segs);
+int pcabi_qual_filter_dev(const uint8_t *qual, int64_t qual_n, const int64_t *span_off, const int32_t *span_len,
+                          int64_t n_reads, int64_t n_segs, const pcabi_qual_opts *opts, pcabi_qual_read *out,
+                          void *scratch, int64_t scratch_len, void *stream);
+int pcabi_qual_filter_host(int device, const uint8_t *qual, int64_t qual_n, const int64_t *span_off,
+                           const int32_t *span_len, int64_t n_reads, const pcabi_qual_opts *opts,
+                           pcabi_qual_read *out);
+void pcabi_qual_error_table(uint64_t *table);
+void pcabi_qual_last_times(int on, int reset, double *ms, int64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif
