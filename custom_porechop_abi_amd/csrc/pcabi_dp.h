@@ -1219,6 +1219,68 @@ PCABI_HD bool packed_ok(int L, int rpl, const Scoring &s) {
     }
 }
 
+// Range conditions of the packed buckets' gap-extend frame (LanePShift below: pk::Lay keys, 36..64
+// rows, affine gaps) for an adapter of L bases in register bucket rpl with rebase period P: the
+// biases B in [blo, bhi] keep every shifted key's score inside the 10-bit field, strictly above the
+// -512 sentinel. The 2-bit tie field is static, so there is no tag condition; the slot bounds are
+// shift_range's (the same recurrences in Lay's frame):
+//   * packed_ok holds (the last column and finish() run Lay itself);
+//   * 2 <= P <= PSHIFT_PMAX = 512: the frame spans at least |ge| P, so no larger power of two can
+//     fit the 1023 values of the field;
+//   * a key of slot s is stored or used at phases -1 (after a rebase) .. P - 1: its shifted score
+//     lies in [lo(s) + |ge| (s - 1) - B, hi(s) + |ge| (s + P - 1) - B] with lo / hi the bounds of H
+//     and the diagonal candidate (below) and of S, G and the diagonal candidate (above); row 0
+//     holds G = OPEN only. The column-0 H key (OPEN - 1) lies between them.
+constexpr int PSHIFT_PMAX = 512;
+PCABI_HD bool pshift_range(int L, int rpl, const Scoring &s, int P, int &blo, int &bhi) {
+    if (rpl < 36 || rpl > 64 || s.go == s.ge || !packed_ok(L, rpl, s)) return false;
+    if (P < 2 || P > PSHIFT_PMAX) return false;
+    const int e = -s.ge, bs = best_sub(s) > 0 ? best_sub(s) : 0;
+    int msub = s.mi < s.ma ? s.mi : s.ma;
+    if (msub > 0) msub = 0;
+    const int off = rpl - L;
+    int lo0 = s.go, hi0 = s.go + e + e * (P - 1);     // row 0: G = OPEN
+    for (int sl = 1; sl <= rpl; ++sl) {
+        const int i = sl - off;
+        const int slo = i >= 1 ? s.go + (i - 1) * s.ge : 0, shi = i >= 1 ? i * bs : 0;
+        const int ulo = i >= 2 ? s.go + (i - 2) * s.ge : 0, uhi = i >= 2 ? (i - 1) * bs : 0;
+        int lo = slo + s.go;                          // H; S, G and the column-0 key lie above (go < 0)
+        if (ulo + msub < lo) lo = ulo + msub;         // diagonal; V lies above H (Slo(i - 1) >= Slo(i))
+        int hi = shi + (s.go + e > 0 ? s.go + e : 0); // S, G; H and V lie below
+        if (uhi + bs > hi) hi = uhi + bs;             // diagonal
+        lo += e * (sl - 1);
+        hi += e * (sl + P - 1);
+        if (lo < lo0) lo0 = lo;
+        if (hi > hi0) hi0 = hi;
+    }
+    blo = hi0 - 511;                                  // hi0 - B <= 511
+    bhi = lo0 + 511;                                  // lo0 - B >= -511
+    return blo <= bhi;
+}
+// One period and one bias for a bucket's adapters: the largest power-of-two period at which the
+// adapters' bias ranges intersect, and the middle of the intersection; false: the bucket keeps Lay.
+PCABI_HD bool pshift_bucket(const int32_t *lens, int n_adp, int rpl, const Scoring &s, int &P, int &B) {
+    if (n_adp < 1) return false;
+    for (int p = PSHIFT_PMAX; p >= 2; p >>= 1) {
+        int lo = -(1 << 30), hi = 1 << 30;
+        bool ok = true;
+        for (int k = 0; k < n_adp && ok; ++k) {
+            int blo, bhi;
+            ok = pshift_range(lens[k], rpl, s, p, blo, bhi);
+            if (ok) {
+                lo = blo > lo ? blo : lo;
+                hi = bhi < hi ? bhi : hi;
+            }
+        }
+        if (ok && lo <= hi) {
+            P = p;
+            B = lo + (hi - lo) / 2;
+            return true;
+        }
+    }
+    return false;
+}
+
 template <int RPL, bool AFFINE, typename LAY = pk::Lay<RPL>, int PD = PCABI_TAB_PD>
 struct LanePacked {
     using Y = LAY;
@@ -1732,6 +1794,178 @@ PCABI_HD Result align_lane_shift4(const TileFn &tr, int n, const TabFn &tabfn, i
         ls.template column<decltype(tabfn(0))>(tabfn((int)((cur >> (8 * ((j - 1) & 3))) & 0xFFu)), j, off);
     }
     return shift_last<RPL, PD>(ls, tabfn((int)((cur >> (8 * ((n - 1) & 3))) & 0xFFu)), n, L, sc);
+}
+
+// ==========================================================================================
+// align_lane_pshift<RPL>: the packed core (pk::Lay, affine gaps) in the gap-extend frame, for the
+// cross-mode launches of the 36..64-row buckets whose adapters all pass pshift_range at one period
+// and bias (pshift_bucket). As in LayS, every key of slot s at column phase jj holds its Lay value
+// with the score moved by f(s, jj) = |ge| (s + jj) - B: a gap extend is the key itself, a gap open
+// costs OPEN = go - ge, a diagonal step sub - go - ge (sub_key_pshift). Lay's 2-bit tie field is
+// static -- stored G keys 0, stored H keys 1, V keys 2, diagonal candidates 3 -- so it needs no
+// scheme of its own: an extend keeps the tie value it was stored with, exactly the value Lay's
+// extend add carries along, and all comparands of one max are keys of the same (s, jj). Per cell 8
+// VALU ops (2 max, 1 max3, 2 or, 1 and, the G add, the next row's diagonal add) against Lay's 10.
+// A rebase (every P columns, uniform) adds ge P to the stored scores and touches nothing else.
+// The inner columns' row-L scout keeps the best key in Lay's frame; before the last column the
+// stored keys go back to Lay keys, and LanePacked<.., Lay>'s last column and finish() run unchanged.
+// ==========================================================================================
+namespace pk {
+template <int RPL, typename AdpFn>
+PCABI_HD int32_t sub_key_pshift(int s, int c, const AdpFn &adp, int off, const Scoring &sc) {
+    using Y = Lay<RPL>;
+    const int d = -sc.go - sc.ge;
+    if (s <= off) return Y::TB3 + Y::sc(d);
+    return (c == adp(s)) ? (Y::sc(sc.ma + d) + Y::TB3 + Y::INC_M) : (Y::sc(sc.mi + d) + Y::TB3 + Y::INC_D);
+}
+constexpr int32_t PSENT = (int32_t)0x80000000;   // score -512, below every shifted value
+}  // namespace pk
+
+template <int RPL, int PD = PCABI_TAB_PD>
+struct LanePShift {
+    using Y = pk::Lay<RPL>;
+    LanePacked<RPL, true, Y, PD> st;   // G, HK, bkey, bj: the frame's keys until to_lay()
+    int32_t kgo;     // sc(OPEN): S key (tie field cleared) -> stored G
+    int32_t ftop;    // sc(f(0, jj)): uniform
+    int32_t k_e;     // sc(|ge|)
+    int32_t k_eR;    // sc(|ge| RPL)
+    int32_t k_rb;    // a rebase: sc(ge P)
+    int jj, P;
+
+    PCABI_HD void init(int L, const Scoring &sc, int P_, int B) {
+        using pk::addw;
+        const int off = RPL - L;
+        P = P_;
+        jj = 0;
+        k_e = Y::sc(-sc.ge);
+        k_eR = Y::sc(-sc.ge * RPL);
+        k_rb = Y::sc(sc.ge * P);
+        ftop = Y::sc(-B);
+        kgo = Y::sc(sc.go - sc.ge);
+        // the per-slot chains below run in a VGPR (vreg): as uniform values they would be 2 RPL live SGPRs
+        int32_t fs = vreg(addw(ftop, kgo));        // sc(f(s, 0) + OPEN)
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            fs = addw(fs, k_e);
+            st.G[s] = addw(Y::start(off - s), fs);   // S(s, 0) = 0; padded (s, 0) reaches real (0, off - s)
+            st.HK[s] = addw(fs, Y::sc(-1)) | Y::TB1; // H(s, 0) = neg_score = OPEN - 1: loses to G in column 1
+        }
+        st.bkey = Y::start(-L);                    // the (L, 0) seed, Lay's frame
+        st.bj = 0;
+    }
+
+    // next column's phase: one column on, a rebase every P columns (uniform branch)
+    PCABI_HD void advance() {
+        using pk::addw;
+        ++jj;
+        ftop = addw(ftop, k_e);
+        if (jj == P) {
+#pragma unroll
+            for (int s = 1; s <= RPL; ++s) {
+                st.G[s] = addw(st.G[s], k_rb);
+                st.HK[s] = addw(st.HK[s], k_rb);
+            }
+            jj = 0;
+            ftop = addw(ftop, k_rb);
+        }
+    }
+
+    // inner column j at phase jj (after advance())
+    template <typename TabRow>
+    PCABI_HD void column(const TabRow &tab, const int j, const int off) {
+        using pk::addw;
+        const int32_t kg = vreg(kgo);              // the cell's add reads a VGPR (vreg)
+        const int32_t top = addw(ftop, kgo);
+        int32_t gup = addw(Y::start(j + off), top);            // G(0, j): S = 0
+        int32_t vup = pk::PSENT;                                // V(0, j)
+        // G(0, j - 1) in the frame of phase jj - 1: f lower by |ge|
+        int32_t diag = addw(addw(Y::start(j - 1 + off), top), pk::negw(k_e));
+        constexpr int NQ = RPL / 4;
+        int32_t t[RPL + 2];
+        if (PD > 0) {
+#pragma unroll
+            for (int q = 0; q <= PD && q < NQ; ++q) tab.quad(q, t + 4 * q + 1);
+        }
+        diag = addw(diag, PD > 0 ? t[1] : tab(1));
+        int32_t lv = 0, ls = 0;
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            if (PD > 0 && (s & 3) == 1) {
+                const int q = (s - 1) / 4 + PD + 1;
+                if (q < NQ) tab.quad(q, t + 4 * q + 1);
+            }
+            int32_t diag_nx = 0;
+            if (s < RPL) diag_nx = st.G[s] + (PD > 0 ? t[s + 1] : tab(s + 1));
+            const int32_t hn = std::max(st.HK[s], st.G[s]);    // extend: the key itself, tb 1 beats the open's 0
+            const int32_t vn2 = std::max(vup, gup) | Y::TB2;   // extend: the key itself, tb 2 beats the open's 0
+            const int32_t sn = max3i(diag, vn2, hn);
+            if (s == RPL) { lv = vn2; ls = sn; }
+            st.G[s] = (sn & ~Y::TBM) + kg;
+            st.HK[s] = hn | Y::TB1;
+            gup = st.G[s];
+            vup = vn2;
+            diag = diag_nx;
+#if defined(__HIP_DEVICE_COMPILE__)
+            if (PCABI_ROW_FENCE > 0 && (s % (PCABI_ROW_FENCE > 0 ? PCABI_ROW_FENCE : 1)) == 0) __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
+        // row-L scout (LanePacked::column_tail): the corrected key goes back to Lay's frame (score
+        // less f(RPL, jj)), then the strict '>' on the scores alone
+        const int32_t corr = addw(std::max(lv | Y::TB3, ls & ~Y::TBM), pk::negw(addw(ftop, k_eR)));
+        const bool upd = corr > (st.bkey | ((1 << Y::SC_SH) - 1));
+        st.bkey = upd ? corr : st.bkey;
+        st.bj = upd ? j : st.bj;
+    }
+
+    // The stored keys of phase jj as Lay keys: the score less f(s, jj), G's gap open go instead of OPEN.
+    PCABI_HD void to_lay(const Scoring &sc) {
+        using pk::addw;
+        using pk::negw;
+        int32_t ch = vreg(negw(ftop));             // VGPR chains, as in init()
+        int32_t cg = addw(ch, Y::sc(sc.ge));
+#pragma unroll
+        for (int s = 1; s <= RPL; ++s) {
+            cg = addw(cg, negw(k_e));
+            ch = addw(ch, negw(k_e));
+            st.G[s] = addw(st.G[s], cg);
+            st.HK[s] = addw(st.HK[s], ch);
+        }
+    }
+};
+
+template <int RPL, int PD = PCABI_TAB_PD, typename ReadFn, typename TabFn>
+PCABI_HD Result align_lane_pshift(ReadFn &rd, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
+    using Y = pk::Lay<RPL>;
+    LanePShift<RPL, PD> ls;
+    const int off = RPL - L;
+    ls.init(L, sc, P, B);
+    int r = rd(1);
+#pragma unroll 1
+    for (int j = 1; j < n; ++j) {
+        const int rn = rd(j + 1);
+        ls.advance();
+        ls.template column<decltype(tabfn(r))>(tabfn(r), j, off);
+        r = rn;
+    }
+    // the stored keys back in Lay's frame, then Lay's last column (its table row is the frame's,
+    // read less a constant: sub_key<Lay> = sub_key_pshift + sc(ge)) and finish()
+    ls.to_lay(sc);
+    auto &st = ls.st;
+    // one column: its adds may read SGPRs (no vreg), which keeps two VGPRs free where the 64-row
+    // bucket's register count peaks
+    st.k_ge = Y::sc(sc.ge);
+    st.k_go = Y::sc(sc.go);
+    st.k_gev = st.k_geh = 0;
+    st.k_gex = st.k_ge;
+    st.k_vo = 0;
+    st.neg2 = Y::sc(pk::neg_score(sc)) | Y::TB2;
+    st.materialize(L);
+    const pk::ShiftRow<decltype(tabfn(r))> row{tabfn(r), Y::sc(sc.ge)};
+    st.template column<decltype(row), true>(row, n, L, off);
+    Best b;
+    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
+    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
+    return finish(b, L, n);
 }
 
 // Long buckets: pass 0 (c, nD) and pass 1 (m) over the same window (two readers, two tables);

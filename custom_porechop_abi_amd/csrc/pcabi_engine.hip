@@ -454,16 +454,26 @@ int bucket_pack_mode(int b, const std::vector<int32_t> &lens, const pcabi::Scori
 }
 
 
-// Whether a cross-mode launch of a run-tagged bucket (bucket_pack_mode 2) runs its inner columns in
-// the gap-extend frame (pcabi_dp.h pk::LayS): every adapter passes shift_ok, at one period (the
-// largest every adapter allows) and one bias (the middle of the ranges' intersection). Sets
-// p.shift_p / p.shift_b (0: the bucket keeps LayT). The chunk, split and pairs launches keep LayT.
+// Whether a cross-mode launch of a run-tagged bucket (bucket_pack_mode 2), or of a packed bucket of
+// 36..64 rows (bucket_pack_mode 1), runs its inner columns in the gap-extend frame (pcabi_dp.h
+// pk::LayS / LanePShift): every adapter passes shift_ok / pshift_range, at one period (the largest
+// every adapter allows) and one bias (the middle of the ranges' intersection). Sets p.shift_p /
+// p.shift_b (0: the bucket keeps LayT / Lay). The chunk, split and pairs launches keep LayT / Lay.
 void bucket_shift(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc, int pack_mode, KParams &p) {
     p.shift_p = p.shift_b = 0;
-    if (pack_mode != 2 || lens.empty() || sc.go == sc.ge) return;
-    const char *e = std::getenv("PCABI_SHIFT");   // PCABI_SHIFT=0: every bucket keeps LayT (A/B measurements)
+    if (lens.empty() || sc.go == sc.ge) return;
+    const char *e = std::getenv("PCABI_SHIFT");   // PCABI_SHIFT=0: every bucket keeps LayT / Lay (A/B measurements)
     if (e && e[0] == '0') return;
     const int rpl = kBuckets[b].rpl;
+    if (pack_mode == 1 && kBuckets[b].kind == FAST && rpl >= 36 && rpl <= 64) {
+        int P, B;
+        if (pcabi::pshift_bucket(lens.data(), (int)lens.size(), rpl, sc, P, B)) {
+            p.shift_p = P;
+            p.shift_b = B;
+        }
+        return;
+    }
+    if (pack_mode != 2) return;
     for (int P = pcabi::shift_pmax(rpl); P >= 2; P >>= 1) {
         int lo = INT32_MIN, hi = INT32_MAX;
         bool ok = true;

@@ -80,7 +80,8 @@ bool chunkable(int b, bool packed);
 int dispatch(int b, const KParams &p, bool affine, hipStream_t st, int packed);
 bool bucket_packed_ok(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc);
 int bucket_pack_mode(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc);
-// cross shape, pack mode 2: the bucket's gap-extend frame into p.shift_p / p.shift_b (0: none)
+// cross shape, pack mode 2, and pack mode 1 at 36..64 rows: the bucket's gap-extend frame into
+// p.shift_p / p.shift_b (0: none)
 void bucket_shift(int b, const std::vector<int32_t> &lens, const pcabi::Scoring &sc, int pack_mode, KParams &p);
 
 // Host-side layout of a bucket's adapter table, for a caller that uploads its own (pcabi_align_host).

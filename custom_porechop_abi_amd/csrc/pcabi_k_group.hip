@@ -2,9 +2,10 @@
 // units of one core family, each a (window set, register bucket) cross product, in one launch.
 // The block's unit is found by a scalar walk over the segment table in the kernel arguments; the
 // unit's rows select the core (a wave-uniform switch), which then runs exactly as k_align's cross
-// mode (cross_block); a class-0 unit whose adapters all pass pcabi::shift_ok runs in the gap-extend
-// frame (GroupSeg::shift_p > 0). The kernel's register count is its largest case's: class 0 (run-tagged, <= 32
-// rows) holds 5 waves per SIMD, class 1 (packed, 36..64 rows) 3.
+// mode (cross_block); a class-0 unit whose adapters all pass pcabi::shift_ok, and a class-1 unit
+// whose adapters pass pcabi::pshift_bucket, runs in the gap-extend frame (GroupSeg::shift_p > 0).
+// The kernel's register count is its largest case's: class 0 (run-tagged, <= 32 rows) holds 5 waves
+// per SIMD, class 1 (packed, 36..64 rows) 3.
 #include "pcabi_kern.h"
 
 namespace pcabi_eng {
@@ -48,10 +49,18 @@ __global__ __launch_bounds__(256) void k_align_group(GroupParams gp) {
             }
         }
     } else {
-        switch (g.rpl) {
-#define P(R) case R: cross_block<R, true, PACKED>(p, lb, wave_tab); break;
-        P(36) P(40) P(44) P(48) P(52) P(56) P(60) P(64)
+        if (g.shift_p > 0) {
+            switch (g.rpl) {
+#define P(R) case R: cross_block<R, true, PSHIFT>(p, lb, wave_tab); break;
+            P(36) P(40) P(44) P(48) P(52) P(56) P(60) P(64)
 #undef P
+            }
+        } else {
+            switch (g.rpl) {
+#define P(R) case R: cross_block<R, true, PACKED>(p, lb, wave_tab); break;
+            P(36) P(40) P(44) P(48) P(52) P(56) P(60) P(64)
+#undef P
+            }
         }
     }
 }

@@ -48,7 +48,8 @@ int fail(int code, const std::string &msg);
 // every adapter to the bucket's longest, rounded up to kStripeTab rows (pcabi_adapters::rt).
 enum Kind { FAST = 0, GENERIC = 1, PACKED = 2, WIDE = 3, LONG = 4, STRIPED = 5,
             TAGGED = 6,     // TAGGED: PACKED with the run-tagged key layout (pcabi_dp.h pk::LayT), a launch-time choice
-            SHIFT = 7 };    // SHIFT: TAGGED in the gap-extend frame (pk::LayS), cross mode, KParams::shift_p > 0
+            SHIFT = 7,      // SHIFT: TAGGED in the gap-extend frame (pk::LayS), cross mode, KParams::shift_p > 0
+            PSHIFT = 8 };   // PSHIFT: PACKED (36..64 rows, affine) in the gap-extend frame (LanePShift), likewise
 struct BucketDef {
     int rpl;
     Kind kind;
@@ -98,8 +99,9 @@ struct KParams {
     // launch's first wave in the task arrays, dev_waves[1] = its wave count; the grid is n_waves
     // blocks that stride over the waves
     const int32_t *dev_waves;
-    // cross mode, run-tagged buckets in the gap-extend frame (pcabi_dp.h shift_ok): the bucket's
-    // rebase period (0: the bucket runs LayT) and bias
+    // cross mode, buckets in the gap-extend frame (pcabi_dp.h shift_ok: run-tagged, <= 32 rows;
+    // pshift_bucket: packed, 36..64 rows): the bucket's rebase period (0: the bucket runs LayT / Lay)
+    // and bias
     int32_t shift_p, shift_b;
 };
 
@@ -197,6 +199,20 @@ __device__ __forceinline__ void fill_wave_tab_shift(const KParams &p, int a_loca
     __syncthreads();
 }
 
+// The packed buckets' gap-extend frame's table (pk::sub_key_pshift), same shape.
+template <int RPL>
+__device__ __forceinline__ void fill_wave_tab_pshift(const KParams &p, int a_local, int L, int32_t *wave_tab) {
+    const int off = RPL - L;
+    const int lane = threadIdx.x & 63;
+    for (int e = lane; e < kTabW * RPL; e += 64) {
+        const int c = e / RPL, srow = e % RPL + 1;
+        const uint32_t *ap = p.adp_pad + (int64_t)a_local * (RPL / 4);
+        auto code = [&](int sl) { return (int)((ap[(sl - 1) / 4] >> (8 * ((sl - 1) & 3))) & 0xFFu); };
+        wave_tab[e] = pcabi::pk::sub_key_pshift<RPL>(srow, c, code, off, p.sc);
+    }
+    __syncthreads();
+}
+
 // The two tables of a long bucket's wave: pass 0 (c, nD) then pass 1 (m), kTabW x RPL each.
 template <int RPL>
 __device__ __forceinline__ void fill_wave_tab_long(const KParams &p, int a_local, int L, int32_t *wave_tab) {
@@ -227,6 +243,7 @@ __device__ __forceinline__ void run_lane(const KParams &p, int a_local, int64_t 
     if constexpr (KIND == PACKED) fill_wave_tab<RPL>(p, a_local, L, wave_tab);
     if constexpr (KIND == TAGGED) fill_wave_tab<RPL, pcabi::pk::LayT<RPL>>(p, a_local, L, wave_tab);
     if constexpr (KIND == SHIFT) fill_wave_tab_shift<RPL>(p, a_local, L, wave_tab);
+    if constexpr (KIND == PSHIFT) fill_wave_tab_pshift<RPL>(p, a_local, L, wave_tab);
     if constexpr (KIND == LONG) fill_wave_tab_long<RPL>(p, a_local, L, wave_tab);
     if (w < 0) return;
     const int n = p.win_len[w];
@@ -269,6 +286,10 @@ __device__ __forceinline__ void run_lane(const KParams &p, int a_local, int64_t 
             static_assert(RPL <= 32 && AFFINE, "gap-extend frame: affine buckets of <= 32 rows");
             auto tabfn = [&](int rc) { return LdsRow{wave_tab + rc * RPL}; };
             r = pcabi::align_lane_shift<RPL>(rd, n, tabfn, L, p.sc, p.shift_p, p.shift_b);
+        } else if constexpr (KIND == PSHIFT) {
+            static_assert(RPL >= 36 && RPL <= 64 && AFFINE, "packed gap-extend frame: affine buckets of 36..64 rows");
+            auto tabfn = [&](int rc) { return LdsRow{wave_tab + rc * RPL}; };
+            r = pcabi::align_lane_pshift<RPL>(rd, n, tabfn, L, p.sc, p.shift_p, p.shift_b);
         } else if constexpr (KIND == LONG) {
             WindowReader rd1 = rd;   // the second pass reads the window again from its start
             auto tab0 = [&](int rc) { return LdsRow{wave_tab + rc * RPL}; };
@@ -298,7 +319,7 @@ __device__ __forceinline__ void run_lane(const KParams &p, int a_local, int64_t 
 //  pairs: grid (ceil(n_waves/4)); wave = one adapter, lanes = host-grouped tasks
 template <int KIND, int RPL>
 constexpr int wave_tab_ints() {
-    return (KIND == PACKED || KIND == TAGGED || KIND == SHIFT) ? kTabW * RPL : (KIND == LONG ? 2 * kTabW * RPL : 1);
+    return (KIND == PACKED || KIND == TAGGED || KIND == SHIFT || KIND == PSHIFT) ? kTabW * RPL : (KIND == LONG ? 2 * kTabW * RPL : 1);
 }
 
 // Cross mode, block b of a (window tiles x adapters) grid. XCD-aware order: workgroups are dealt to
@@ -770,7 +791,7 @@ struct GroupSeg {
     int64_t block0;            // the unit's first block in the launch
     int32_t n_adp;
     int32_t rpl;
-    int32_t shift_p, shift_b;  // class 0: KParams::shift_p / shift_b of the unit
+    int32_t shift_p, shift_b;  // KParams::shift_p / shift_b of the unit
 };
 struct GroupParams {
     GroupSeg seg[kMaxGroupSegs];
@@ -818,7 +839,7 @@ void dispatch_chunk_group(const ChunkGroupParams &gp, unsigned blocks, hipStream
 // (cross mode with p.shift_p > 0: in the gap-extend frame, k_align<.., SHIFT>)
 void dispatch_packed_small(int rpl, const KParams &p, bool affine, dim3 grid, hipStream_t st, bool tagged);
 void dispatch_packed_large(int rpl, bool long_kind, const KParams &p, bool affine, dim3 grid,
-                           hipStream_t st);                                                   // PACKED 36..88, LONG
+                           hipStream_t st);   // PACKED 36..88 (cross mode with p.shift_p > 0: PSHIFT), LONG
 void dispatch_fast(int rpl, bool generic, const KParams &p, bool affine, dim3 grid, hipStream_t st);
 // k_align_chunk launches (middle-scan candidates in owned-column chunks), striped bucket included;
 // tagged: the bucket runs the run-tagged layout (bucket_pack_mode 2)
