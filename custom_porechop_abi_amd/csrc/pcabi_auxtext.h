@@ -1,6 +1,6 @@
 // pcabi_auxtext.h -- the SAM text of BAM aux chains, and text records (FASTQ / FASTA) that carry it in
 // their headers: the tag walk, the guards, the digit rule and the byte emitters (pcabi_auxtext.hip,
-// pcabi_io.cpp; include/pcabi.h pcabi_auxtext_*, pcabi_fastx_pack_*; DESIGN.md "Tags in text headers").
+// pcabi_write.cpp; include/pcabi.h pcabi_auxtext_*, pcabi_fastx_pack_*; DESIGN.md "Tags in text headers").
 // Nothing here is device-only: the kernels, the host build (device < 0) and the CPU tests
 // (tests/auxtext_fuzz_main.cpp builds it alone) run the same code.
 //

@@ -335,8 +335,7 @@ struct WriteDev {
     PinBuf<> p_z;
     Stream st;
     AuxDev aux;
-    ModsDev *mods = nullptr;
-    MovesDev *moves = nullptr;
+    RemapDev remap;
 };
 WriteDev &g_wd = *new WriteDev;
 std::mutex g_wd_mu;
@@ -352,8 +351,7 @@ int64_t pcabi_internal::fastx_write_tags_dev(int device, const uint8_t *seq, int
     if (g_wd.device >= 0 && g_wd.device != device) {
         (void)hipSetDevice(g_wd.device);
         g_wd.st.release();
-        mods_dev_free(g_wd.mods);
-        moves_dev_free(g_wd.moves);
+        g_wd.remap.release();
         g_wd = WriteDev();
     }
     PCABI_TRY(hipSetDevice(device));
@@ -366,19 +364,7 @@ int64_t pcabi_internal::fastx_write_tags_dev(int device, const uint8_t *seq, int
     // steps 1, 2: the letters up, the remapped tags sized in one round trip (as the BAM writer does)
     if (int rc = g_wd.seq.reserve(seq_n + 64, grow(seq_n + 64))) return rc;
     if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(g_wd.seq, seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
-    if (moves) {
-        if (!g_wd.moves) g_wd.moves = moves_dev_new();
-        if (int rc = moves_check(*moves)) return rc;
-        if (int rc = moves_dev_plan_begin(g_wd.moves, st, *moves)) return rc;
-    }
-    if (mods) {
-        if (!g_wd.mods) g_wd.mods = mods_dev_new();
-        if (int rc = mods_plan_any(device, g_wd.mods, nullptr, st, seq, g_wd.seq, seq_n, mods->tags, mods->tags_n, mods->reads,
-                                   mods->n_reads, mods->parts, mods->n_parts, mods->usable))
-            return rc;
-    }
-    if (moves)
-        if (int rc = moves_dev_plan_end(g_wd.moves, st, *moves)) return rc;
+    if (int rc = g_wd.remap.plan(device, st, seq, g_wd.seq, seq_n, mods, moves)) return rc;
     // step 3: the side blob with its gaps, the parts
     FastxWriteJob job;
     layout(&job);
@@ -400,10 +386,7 @@ int64_t pcabi_internal::fastx_write_tags_dev(int device, const uint8_t *seq, int
     if (int rc = g_wd.qual.reserve(qual_n + 64, grow(qual_n + 64))) return rc;
     if (side_n > 0) PCABI_TRY(hipMemcpyAsync(g_wd.side, job.side, (size_t)side_n, hipMemcpyHostToDevice, st));
     if (qual_n > 0 && !fasta) PCABI_TRY(hipMemcpyAsync(g_wd.qual, qual, (size_t)qual_n, hipMemcpyHostToDevice, st));
-    if (mods)
-        if (int rc = mods_dev_write(g_wd.mods, st, mods->parts, mods->n_parts, g_wd.side, side_n)) return rc;
-    if (moves)
-        if (int rc = moves_dev_write(g_wd.moves, st, moves->parts, moves->n_parts, g_wd.side, side_n)) return rc;
+    if (int rc = g_wd.remap.write(st, mods, moves, g_wd.side, side_n)) return rc;
     // step 5: every part's text length
     std::vector<pcabi_auxtext_part> ap((size_t)n_parts);
     for (int64_t i = 0; i < n_parts; ++i) ap[(size_t)i] = pcabi_auxtext_part{job.parts[i].aux_off, 0, 0, job.parts[i].aux_len, 0};

@@ -1,4 +1,4 @@
-// pcabi_bam.h -- the record layer of unaligned BAM input and output (pcabi_bam.hip, pcabi_io.cpp; the
+// pcabi_bam.h -- the record layer of unaligned BAM input and output (pcabi_bam.hip, pcabi_io.cpp, pcabi_write.cpp; the
 // pack half for output is at the end of the file). Input: the header
 // skip, the record walk and the unpack of one record's bases into the reader's batch layout (sequence
 // letters, qualities, Dna5 codes). Nothing here is device-only: the kernel (k_bam_unpack), the host

@@ -301,7 +301,7 @@ int bam_dev_unpack(BamDev *b, const pcabi_bam_rec *recs, int64_t n_recs, const L
     return 0;
 }
 
-// ---- the device half of the BAM writer (csrc/pcabi_io.cpp) ---------------------------------------
+// ---- the device half of the BAM writer (csrc/pcabi_write.cpp) ------------------------------------
 // head[0, head_n) (the file header, or nothing) and the record chain of `parts` (planned from head_n)
 // form one stream of stream_n bytes in device memory: the text, the table and the side blob go up,
 // k_bam_pack writes the chain, the BGZF encoder (pcabi_bgzf_dev) reads it there in members of 65280
@@ -316,8 +316,7 @@ struct PackDev {
     DevBuf<int64_t> d_len;
     PinBuf<> p_z;      // the compressed bytes, pinned
     Stream st;
-    ModsDev *mods = nullptr;   // the remap's device side (pcabi_mods.hip), made at its first use
-    MovesDev *moves = nullptr; // the move tables' (pcabi_moves.hip), likewise
+    RemapDev remap;    // the remap stage's device side (pcabi_hostdev.h)
 };
 // kept for the process and never destroyed (a deliberate leak): a destructor at exit would call into a
 // HIP runtime that may already have shut down
@@ -334,8 +333,7 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
     if (g_pack.device >= 0 && g_pack.device != device) {
         (void)hipSetDevice(g_pack.device);
         g_pack.st.release();
-        mods_dev_free(g_pack.mods);
-        moves_dev_free(g_pack.moves);
+        g_pack.remap.release();
         g_pack = PackDev();
     }
     PCABI_TRY(hipSetDevice(device));
@@ -347,21 +345,8 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
     // the letters first: the remap counts them where the pack reads them
     if (int rc = g_pack.buf[0].reserve(seq_n + 64, std::max<int64_t>(seq_n + 64 + seq_n / 4, 1 << 20))) return rc;
     if (seq_n > 0) PCABI_TRY(hipMemcpyAsync(g_pack.buf[0], seq, (size_t)seq_n, hipMemcpyHostToDevice, st));
-    // the tags to remap are sized in one round trip: the move tables' stages are queued, the
-    // modification tags' plan runs behind them and waits for the stream, then the lengths are read
-    if (moves) {
-        if (!g_pack.moves) g_pack.moves = moves_dev_new();
-        if (int rc = moves_check(*moves)) return rc;
-        if (int rc = moves_dev_plan_begin(g_pack.moves, st, *moves)) return rc;
-    }
-    if (mods) {
-        if (!g_pack.mods) g_pack.mods = mods_dev_new();
-        if (int rc = mods_plan_any(device, g_pack.mods, nullptr, st, seq, g_pack.buf[0], seq_n, mods->tags, mods->tags_n, mods->reads,
-                                   mods->n_reads, mods->parts, mods->n_parts, mods->usable))
-            return rc;
-    }
-    if (moves)
-        if (int rc = moves_dev_plan_end(g_pack.moves, st, *moves)) return rc;
+    // the tags to remap are sized in one round trip
+    if (int rc = g_pack.remap.plan(device, st, seq, g_pack.buf[0], seq_n, mods, moves)) return rc;
     if (mods || moves) (*layout)(&job);
     const uint8_t *head = job.head, *side = job.side;
     const pcabi_bam_part *parts = job.parts;
@@ -384,10 +369,7 @@ int64_t write_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *
     if (n_parts > 0)
         PCABI_TRY(hipMemcpyAsync(d_parts, parts, (size_t)n_parts * sizeof(pcabi_bam_part), hipMemcpyHostToDevice, st));
     if (head_n > 0) PCABI_TRY(hipMemcpyAsync(d_stream, head, (size_t)head_n, hipMemcpyHostToDevice, st));
-    if (mods)
-        if (int rc = mods_dev_write(g_pack.mods, st, mods->parts, mods->n_parts, d_side, side_n)) return rc;
-    if (moves)
-        if (int rc = moves_dev_write(g_pack.moves, st, moves->parts, moves->n_parts, d_side, side_n)) return rc;
+    if (int rc = g_pack.remap.write(st, mods, moves, d_side, side_n)) return rc;
     const bool prof = prof_on();
     void *sp = prof ? prof_begin(st, 4) : nullptr;
     if (int rc = launch_pack(st, d_seq, seq_n, d_qual, qual_n, d_side, side_n, d_parts, n_parts, n_tiles, d_stream, stream_n))

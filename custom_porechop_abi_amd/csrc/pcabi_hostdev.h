@@ -1,8 +1,9 @@
 // pcabi_hostdev.h -- the host plumbing the file path's device stages share (pcabi_deflate.hip,
-// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_auxparse.hip, pcabi_qual.hip, pcabi_io.cpp): the error macro, the pinned-memory copy, the clock,
-// the owner of a device or pinned buffer, the owner of a stream, and the declarations of every
-// pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
-// compiles with a plain C++ compiler (pcabi_io.cpp, tests/hostdev_main.cpp).
+// pcabi_inflate.hip, pcabi_bam.hip, pcabi_mods.hip, pcabi_moves.hip, pcabi_auxtext.hip, pcabi_auxparse.hip, pcabi_qual.hip,
+// pcabi_io.cpp, pcabi_write.cpp): the error macro, the pinned-memory copy, the clock, the owner of a device
+// or pinned buffer, the owner of a stream, the owners of a writer's remap stage, and the declarations of
+// every pcabi_internal function that crosses a unit. What names a HIP type sits under __HIPCC__; the rest
+// compiles with a plain C++ compiler (pcabi_io.cpp, pcabi_write.cpp, tests/hostdev_main.cpp).
 #pragma once
 
 #include <time.h>
@@ -11,6 +12,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -250,25 +252,20 @@ struct BamWriteJob {
     const pcabi_bam_part *parts = nullptr;
     int64_t head_n = 0, side_n = 0, n_parts = 0, n_tiles = 0, stream_n = 0;
 };
-struct ModsTables {
+// the tags to remap, of either kind: the tag blob, the tables, the reads' flags (ModsTables: pcabi_mods.hip,
+// MovesTables: pcabi_moves.hip)
+template <class Read, class Part>
+struct TagTables {
     const uint8_t *tags = nullptr;
     int64_t tags_n = 0;
-    const pcabi_mods_read *reads = nullptr;
+    const Read *reads = nullptr;
     int64_t n_reads = 0;
-    pcabi_mods_part *parts = nullptr;
+    Part *parts = nullptr;
     int64_t n_parts = 0;
     uint8_t *usable = nullptr;
 };
-// the move tables to remap (pcabi_moves.hip): the tag blob, the tables, the reads' flags
-struct MovesTables {
-    const uint8_t *tags = nullptr;
-    int64_t tags_n = 0;
-    const pcabi_moves_read *reads = nullptr;
-    int64_t n_reads = 0;
-    pcabi_moves_part *parts = nullptr;
-    int64_t n_parts = 0;
-    uint8_t *usable = nullptr;
-};
+using ModsTables = TagTables<pcabi_mods_read, pcabi_mods_part>;
+using MovesTables = TagTables<pcabi_moves_read, pcabi_moves_part>;
 // mods and moves: either may be null, not both; the two are sized in one round trip before `layout` runs
 int64_t bam_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *qual, int64_t qual_n, const ModsTables *mods,
                            const MovesTables *moves, const std::function<void(BamWriteJob *)> &layout,
@@ -277,7 +274,7 @@ int64_t bam_write_tags_dev(int device, const uint8_t *seq, int64_t seq_n, const 
 void prof_add_bytes(int kind, int64_t bytes);
 
 // ---- pcabi_io.cpp --------------------------------------------------------------------------------
-int io_thread_count();
+int io_thread_count();   // the threads a host stage fans out to (PCABI_IO_THREADS)
 
 // ---- pcabi_mods.hip ------------------------------------------------------------------------------
 // the device half of the remap: the tag blob, the tables and the scratch tables of the plan before
@@ -287,13 +284,10 @@ struct ModsHost;
 // device < 0: the host build; else dev / stream / d_seq name the device side. Checks the tables
 // (PCABI_E_ARG), fills parts[].len and usable[], counts the reads.
 int mods_plan_any(int device, ModsDev *dev, ModsHost *keep, void *stream, const uint8_t *seq, const uint8_t *d_seq, int64_t seq_n,
-                  const uint8_t *tags, int64_t tags_n, const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts,
-                  int64_t n_parts, uint8_t *usable);
-int mods_dev_plan(ModsDev *d, void *stream, const uint8_t *d_seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
-                  const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts, int64_t n_parts, uint8_t *usable);
+                  const ModsTables &t);
+int mods_dev_plan(ModsDev *d, void *stream, const uint8_t *d_seq, int64_t seq_n, const ModsTables &t);
 int mods_dev_write(ModsDev *d, void *stream, const pcabi_mods_part *parts, int64_t n_parts, uint8_t *d_out, int64_t out_cap);
-void mods_write_host(ModsHost *keep, const uint8_t *seq, const uint8_t *tags, const pcabi_mods_read *reads, int64_t n_reads,
-                     const pcabi_mods_part *parts, int64_t n_parts, uint8_t *out);
+void mods_write_host(ModsHost *keep, const uint8_t *seq, const ModsTables &t, uint8_t *out);
 ModsHost *mods_host_new();
 void mods_host_free(ModsHost *h);
 ModsDev *mods_dev_new();
@@ -322,6 +316,68 @@ void moves_host_free(MovesHost *h);
 MovesDev *moves_dev_new();
 void moves_dev_free(MovesDev *d);   // its device current
 int64_t moves_host_ns(int reset, int64_t *dev_plan_ns);   // pcabi_moves_last_times
+
+// ---- the remap stage of a writer: both kinds of tags sized, then written into the side blob's gaps ----
+// (mods / moves: the tables of the kind, null when the batch has none to remap)
+struct RemapFree {
+    void operator()(ModsHost *h) const { mods_host_free(h); }
+    void operator()(MovesHost *h) const { moves_host_free(h); }
+    void operator()(ModsDev *d) const { mods_dev_free(d); }
+    void operator()(MovesDev *d) const { moves_dev_free(d); }
+};
+// The host build: plan() sizes the parts' tags (parts[].len, usable[]) and returns the first non-zero
+// code; write() fills the gaps the caller then laid out (parts[].out) in side and lets the plan go.
+struct RemapHost {
+    std::unique_ptr<ModsHost, RemapFree> mh;
+    std::unique_ptr<MovesHost, RemapFree> vh;
+    const uint8_t *seq = nullptr;
+    const ModsTables *mods = nullptr;
+    const MovesTables *moves = nullptr;
+    int plan(const uint8_t *seq_, int64_t seq_n, const ModsTables *mods_, const MovesTables *moves_) {
+        seq = seq_, mods = mods_, moves = moves_;
+        if (mods) {
+            mh.reset(mods_host_new());
+            if (int rc = mods_plan_any(-1, nullptr, mh.get(), nullptr, seq, nullptr, seq_n, *mods)) return rc;
+        }
+        if (moves) {
+            vh.reset(moves_host_new());
+            if (int rc = moves_plan_host(vh.get(), *moves)) return rc;
+        }
+        return 0;
+    }
+    void write(uint8_t *side) {
+        if (mods) mods_write_host(mh.get(), seq, *mods, side);
+        if (moves) moves_write_host(vh.get(), *moves, side);
+        mh.reset(), vh.reset();
+    }
+};
+// The device: kept by a writer's device side between calls, made at its first use. plan() sizes both kinds
+// in one round trip on `stream` (the letters lie at d_seq already): the move tables' stages are queued, the
+// modification tags' plan runs behind them and waits for the stream, then the lengths are read. write()
+// queues the kernels that fill the gaps of the blob's device copy. release(): its device current.
+struct RemapDev {
+    std::unique_ptr<ModsDev, RemapFree> md;
+    std::unique_ptr<MovesDev, RemapFree> vd;
+    int plan(int device, void *stream, const uint8_t *seq, const uint8_t *d_seq, int64_t seq_n, const ModsTables *mods,
+             const MovesTables *moves) {
+        if (moves) {
+            if (!vd) vd.reset(moves_dev_new());
+            if (int rc = moves_check(*moves)) return rc;
+            if (int rc = moves_dev_plan_begin(vd.get(), stream, *moves)) return rc;
+        }
+        if (mods) {
+            if (!md) md.reset(mods_dev_new());
+            if (int rc = mods_plan_any(device, md.get(), nullptr, stream, seq, d_seq, seq_n, *mods)) return rc;
+        }
+        return moves ? moves_dev_plan_end(vd.get(), stream, *moves) : 0;
+    }
+    int write(void *stream, const ModsTables *mods, const MovesTables *moves, uint8_t *d_side, int64_t side_n) {
+        if (mods)
+            if (int rc = mods_dev_write(md.get(), stream, mods->parts, mods->n_parts, d_side, side_n)) return rc;
+        return moves ? moves_dev_write(vd.get(), stream, moves->parts, moves->n_parts, d_side, side_n) : 0;
+    }
+    void release() { md.reset(), vd.reset(); }
+};
 
 // ---- pcabi_deflate.hip ---------------------------------------------------------------------------
 // pcabi_bgzf_dev with a block list (device pointer, n_blocks + 1 entries, every block 1..65280 bytes):

@@ -1,6 +1,6 @@
 // pcabi_mods.h -- base-modification tags (MM / ML / MN, SAMtags "Base modifications") remapped onto
 // parts of a read: the MM grammar, the usability checks and the per-part rule (pcabi_mods.hip,
-// pcabi_io.cpp; include/pcabi.h pcabi_mods_*; DESIGN.md "BAM output"). Nothing here is device-only: the
+// pcabi_write.cpp; include/pcabi.h pcabi_mods_*; DESIGN.md "BAM output"). Nothing here is device-only: the
 // kernels, the host build (device < 0) and the CPU tests (tests/mods_fuzz_main.cpp builds it alone) run
 // the same code. What differs is the walk over the tag text: parse() goes byte by byte, the kernel takes
 // 64 bytes a pass and gets every byte's group start and counts state from ballots; both judge a byte with

@@ -377,19 +377,17 @@ ModsDev *mods_dev_new() { return new ModsDev; }
 void mods_dev_free(ModsDev *d) { delete d; }
 
 int mods_plan_any(int device, ModsDev *dev, ModsHost *keep, void *stream, const uint8_t *seq, const uint8_t *d_seq, int64_t seq_n,
-                  const uint8_t *tags, int64_t tags_n, const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts,
-                  int64_t n_parts, uint8_t *usable) {
-    if (int rc = check_tables(seq_n, tags_n, reads, n_reads, parts, n_parts)) return rc;
-    for (int64_t j = 0; j < n_parts; ++j) parts[j].len = 0;
-    if (device < 0) plan_host(seq, tags, reads, n_reads, parts, n_parts, usable, nullptr, keep);
-    else if (int rc = mods_dev_plan(dev, stream, d_seq, seq_n, tags, tags_n, reads, n_reads, parts, n_parts, usable)) return rc;
-    count_reads(usable, n_reads);
+                  const ModsTables &t) {
+    if (int rc = check_tables(seq_n, t.tags_n, t.reads, t.n_reads, t.parts, t.n_parts)) return rc;
+    for (int64_t j = 0; j < t.n_parts; ++j) t.parts[j].len = 0;
+    if (device < 0) plan_host(seq, t.tags, t.reads, t.n_reads, t.parts, t.n_parts, t.usable, nullptr, keep);
+    else if (int rc = mods_dev_plan(dev, stream, d_seq, seq_n, t)) return rc;
+    count_reads(t.usable, t.n_reads);
     return 0;
 }
 
-void mods_write_host(ModsHost *keep, const uint8_t *seq, const uint8_t *tags, const pcabi_mods_read *reads, int64_t n_reads,
-                     const pcabi_mods_part *parts, int64_t n_parts, uint8_t *out) {
-    plan_host(seq, tags, reads, n_reads, const_cast<pcabi_mods_part *>(parts), n_parts, nullptr, out, keep);
+void mods_write_host(ModsHost *keep, const uint8_t *seq, const ModsTables &t, uint8_t *out) {
+    plan_host(seq, t.tags, t.reads, t.n_reads, t.parts, t.n_parts, nullptr, out, keep);
 }
 
 ModsHost *mods_host_new() { return new ModsHost; }
@@ -397,8 +395,8 @@ void mods_host_free(ModsHost *h) { delete h; }
 
 // The device half: the tag blob and the tables go up (the letters are the caller's, already there), the
 // plan kernel runs on `stream`, the parts' lengths and the reads' flags come back. Synchronises.
-int mods_dev_plan(ModsDev *d, void *stream, const uint8_t *d_seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
-                  const pcabi_mods_read *reads, int64_t n_reads, pcabi_mods_part *parts, int64_t n_parts, uint8_t *usable) {
+int mods_dev_plan(ModsDev *d, void *stream, const uint8_t *d_seq, int64_t seq_n, const ModsTables &t) {
+    const auto [tags, tags_n, reads, n_reads, parts, n_parts, usable] = t;
     hipStream_t st = (hipStream_t)stream;
     const double t_begin = now_s();
     d->n_reads = d->n_parts = d->n_ents = d->tags_n = 0;
@@ -472,16 +470,17 @@ int pcabi_mods_plan(int device, const uint8_t *seq, int64_t seq_n, const uint8_t
     if (seq_n < 0 || tags_n < 0 || n_reads < 0 || n_parts < 0 || (seq_n > 0 && !seq) || (tags_n > 0 && !tags) ||
         (n_reads > 0 && (!reads || !usable)) || (n_parts > 0 && !parts))
         return fail(PCABI_E_ARG, "bad arguments");
+    const ModsTables t{tags, tags_n, reads, n_reads, parts, n_parts, usable};
     if (device < 0) {
         ModsHost keep;
-        return mods_plan_any(-1, nullptr, &keep, nullptr, seq, nullptr, seq_n, tags, tags_n, reads, n_reads, parts, n_parts, usable);
+        return mods_plan_any(-1, nullptr, &keep, nullptr, seq, nullptr, seq_n, t);
     }
     PCABI_TRY(hipSetDevice(device));
     DevBuf<> d_seq;
     ModsDev dev;
     if (int rc = d_seq.reserve(seq_n + 64, seq_n + 64)) return rc;
     if (seq_n > 0) PCABI_TRY(hipMemcpy(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice));
-    return mods_plan_any(device, &dev, nullptr, nullptr, seq, d_seq, seq_n, tags, tags_n, reads, n_reads, parts, n_parts, usable);
+    return mods_plan_any(device, &dev, nullptr, nullptr, seq, d_seq, seq_n, t);
 }
 
 int pcabi_mods_remap(int device, const uint8_t *seq, int64_t seq_n, const uint8_t *tags, int64_t tags_n,
@@ -507,7 +506,7 @@ int pcabi_mods_remap(int device, const uint8_t *seq, int64_t seq_n, const uint8_
     for (size_t k = 1; k < spans.size(); ++k)
         if (spans[k].first < spans[k - 1].second) return fail(PCABI_E_ARG, "two parts' outputs overlap");
     if (device < 0) {
-        mods_write_host(&keep, seq, tags, reads, n_reads, parts, n_parts, out);
+        plan_host(seq, tags, reads, n_reads, const_cast<pcabi_mods_part *>(parts), n_parts, nullptr, out, &keep);
         return 0;
     }
     PCABI_TRY(hipSetDevice(device));
@@ -520,7 +519,7 @@ int pcabi_mods_remap(int device, const uint8_t *seq, int64_t seq_n, const uint8_
     if (int rc = d_out.reserve((int64_t)stage.size(), (int64_t)stage.size())) return rc;
     if (seq_n > 0) PCABI_TRY(hipMemcpy(d_seq, seq, (size_t)seq_n, hipMemcpyHostToDevice));
     PCABI_TRY(hipMemcpy(d_out, stage.data(), stage.size(), hipMemcpyHostToDevice));
-    if (int rc = mods_dev_plan(&dev, nullptr, d_seq, seq_n, tags, tags_n, reads, n_reads, mine.data(), n_parts, usable.data())) return rc;
+    if (int rc = mods_dev_plan(&dev, nullptr, d_seq, seq_n, ModsTables{tags, tags_n, reads, n_reads, mine.data(), n_parts, usable.data()})) return rc;
     for (int64_t j = 0; j < n_parts; ++j)
         if (mine[(size_t)j].len != parts[j].len) return fail(PCABI_E_DEVICE, "k_mods_plan and the host build disagree on part " + std::to_string(j));
     if (int rc = mods_dev_write(&dev, nullptr, parts, n_parts, d_out + kGuard, out_cap)) return rc;

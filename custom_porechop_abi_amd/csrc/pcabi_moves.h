@@ -1,5 +1,5 @@
 // pcabi_moves.h -- the basecaller's move table (mv) and its sample offset (ts) remapped onto parts of a
-// read: the usability checks, the slice rule and the byte emitters (pcabi_moves.hip, pcabi_io.cpp;
+// read: the usability checks, the slice rule and the byte emitters (pcabi_moves.hip, pcabi_write.cpp;
 // include/pcabi.h pcabi_moves_*; DESIGN.md "BAM output"). Nothing here is device-only: the kernels, the
 // host build (device < 0) and the CPU tests (tests/moves_fuzz_main.cpp builds it alone) run the same code.
 //

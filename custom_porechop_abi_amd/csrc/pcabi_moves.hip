@@ -442,22 +442,13 @@ int moves_dev_write(MovesDev *d, void *stream, const pcabi_moves_part *parts, in
 
 }  // namespace pcabi_internal
 
-namespace {
-MovesTables tables_of(const uint8_t *tags, int64_t tags_n, const pcabi_moves_read *reads, int64_t n_reads, pcabi_moves_part *parts,
-                      int64_t n_parts, uint8_t *usable) {
-    MovesTables t;
-    t.tags = tags, t.tags_n = tags_n, t.reads = reads, t.n_reads = n_reads, t.parts = parts, t.n_parts = n_parts, t.usable = usable;
-    return t;
-}
-}  // namespace
-
 extern "C" {
 
 int pcabi_moves_plan(int device, const uint8_t *tags, int64_t tags_n, const pcabi_moves_read *reads, int64_t n_reads,
                      pcabi_moves_part *parts, int64_t n_parts, uint8_t *usable) {
     if (tags_n < 0 || n_reads < 0 || n_parts < 0 || (tags_n > 0 && !tags) || (n_reads > 0 && (!reads || !usable)) || (n_parts > 0 && !parts))
         return fail(PCABI_E_ARG, "bad arguments");
-    const MovesTables t = tables_of(tags, tags_n, reads, n_reads, parts, n_parts, usable);
+    const MovesTables t{tags, tags_n, reads, n_reads, parts, n_parts, usable};
     if (device < 0) {
         MovesHost keep;
         return moves_plan_host(&keep, t);
@@ -503,7 +494,7 @@ int pcabi_moves_remap(int device, const uint8_t *tags, int64_t tags_n, const pca
     MovesDev dev;
     if (int rc = d_out.reserve((int64_t)stage.size(), (int64_t)stage.size())) return rc;
     PCABI_TRY(hipMemcpy(d_out, stage.data(), stage.size(), hipMemcpyHostToDevice));
-    const MovesTables t = tables_of(tags, tags_n, reads, n_reads, mine.data(), n_parts, usable.data());
+    const MovesTables t{tags, tags_n, reads, n_reads, mine.data(), n_parts, usable.data()};
     if (int rc = moves_dev_plan_begin(&dev, nullptr, t)) return rc;
     PCABI_TRY(hipStreamSynchronize(nullptr));
     for (int64_t j = 0; j < n_parts; ++j)

@@ -1,7 +1,7 @@
 """Sequence-file I/O on both sides of the alignment engine (mirror of porechop_abi/misc.py:60-168
 and the read loading / output of porechop_abi/porechop_abi.py:133-187, 535-668).
 
-The parsing and writing run in libpcabi's native host unit (csrc/pcabi_io.cpp: zlib, the
+The parsing and writing run in libpcabi's native host units (csrc/pcabi_io.cpp, csrc/pcabi_write.cpp: zlib, the
 reference's parse rules, NanoporeRead's normalisation); this module is the Python surface:
   * load_fasta_or_fastq(filename) -> (records, 'FASTA' | 'FASTQ'), the reference's tuples
     (FASTA: (short_name, seq, full_name); FASTQ: (short_name, seq, spacer, quals, full_name));

@@ -597,7 +597,7 @@ int pcabi_kmer_approx_host(int device, const uint8_t *codes, int64_t codes_len, 
                            uint64_t *counts);
 
 /*
- * Sequence files (host code, csrc/pcabi_io.cpp; replaces porechop_abi/misc.py:60-168
+ * Sequence files (host code: the reader csrc/pcabi_io.cpp, the writers csrc/pcabi_write.cpp; replaces porechop_abi/misc.py:60-168
  * load_fasta_or_fastq and NanoporeRead's normalisation, nanopore_read.py:31-44, for the batched
  * path, and NanoporeRead.get_fasta / get_fastq, nanopore_read.py:84-156, for output).
  *   pcabi_fastx_open / next / close : streaming reader, plain or gzip, FASTA, FASTQ (by the
@@ -912,7 +912,7 @@ int pcabi_bam_unpack_host(int device, const uint8_t *bam, int64_t n, const pcabi
                           int64_t codes_cap, int64_t tail_off);
 void pcabi_bam_last_times(int on, int reset, double *ms, int64_t *bytes);
 
-/* ---- unaligned BAM output (csrc/pcabi_bam.h, csrc/pcabi_bam.hip, csrc/pcabi_io.cpp) ----------
+/* ---- unaligned BAM output (csrc/pcabi_bam.h, csrc/pcabi_bam.hip, csrc/pcabi_write.cpp) -------
  * The inverse of the unpack: parts of a batch (whole reads, trimmed reads, split pieces) laid out as
  * a chain of unmapped BAM records. One pcabi_bam_part per output record; a record is
  *   block_size | refID -1 | pos -1 | l_read_name = name_len + 1 | mapq 0 | bin 4680 | n_cigar_op 0 |

@@ -119,6 +119,33 @@ def test_long_header_spans_blocks(gpu_lib, tmp_path):
         assert head.endswith(b'\tts:i:%d' % (100 + 6 * 2000)) and len(head) > 590000
 
 
+def test_bam_and_text_writers_keep_their_device_state_apart(gpu_lib, tmp_path, tmp_path_factory):
+    """The BAM writer and the tagged text writer each keep a remap stage on the device between calls. One
+    process, one small batch (a dozen reads of at most 200 bases with MM / ML and mv / ts, both trims and a
+    split): BAM, then tagged fastq.gz, then BAM again, all on the device. Each file inflates to what the host
+    path writes for the same options, and the second BAM is the first byte for byte."""
+    from custom_porechop_abi_amd import misc
+    from tests import test_writer_errors_cpu as W
+    batch, base = W.case(tmp_path_factory)
+    kw = dict(base, keep_aux=True, keep_mods=True, keep_moves=True)
+
+    def written(name, fmt, gzip_device, **more):
+        path = str(tmp_path / name)
+        assert misc.write_reads(batch, path, fmt, gzip_device=gzip_device, **kw, **more) == batch.n
+        with open(path, 'rb') as f:
+            return f.read()
+
+    bam1 = written('dev1.bam', 'bam', 0)
+    text = written('dev.fastq.gz', 'fastq.gz', 0, header_tags=True)
+    bam2 = written('dev2.bam', 'bam', 0)
+    host_bam = gzip.decompress(written('host.bam', 'bam', None))
+    host_text = gzip.decompress(written('host.fastq.gz', 'fastq.gz', None, header_tags=True))
+    assert b'\tMM:Z:' in host_text and b'\tmv:B:c,' in host_text and b'read5_2' in host_text
+    assert gzip.decompress(bam1) == host_bam
+    assert gzip.decompress(text) == host_text
+    assert bam2 == bam1
+
+
 # ---- the pipeline -----------------------------------------------------------------------------------------------
 def test_file_trimmer_header_tags(gpu_lib, tmp_path):
     """FileTrimmer(keep_tags, header_tags) from a .bam to .fastq: record by record the header parses to the

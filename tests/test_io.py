@@ -1,4 +1,4 @@
-"""Sequence-file I/O (csrc/pcabi_io.cpp through custom_porechop_abi_amd/misc.py) vs the
+"""Sequence-file I/O (csrc/pcabi_io.cpp and csrc/pcabi_write.cpp through custom_porechop_abi_amd/misc.py) vs the
 reference's own code on the same files (tests/golden/g3_io.json.gz, tools/make_golden_g3.py):
   * misc.load_fasta_or_fastq == porechop_abi.misc.load_fasta_or_fastq (misc.py:108-165), on the
     reference's test files and on edge cases (CRLF / lone CR endings, blank and whitespace lines,
