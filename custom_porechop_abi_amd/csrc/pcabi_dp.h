@@ -1151,7 +1151,7 @@ PCABI_HD bool layt_ok(int L, int rpl, const Scoring &s) {
 // Range conditions of the gap-extend frame (pk::LayS) for an adapter of L bases in register bucket
 // rpl with rebase period P: the biases B in [blo, bhi] keep every shifted key's score inside the
 // 8-bit field, strictly above the -128 sentinel. false: none does, or the tags do not fit.
-//   * layt_ok holds (the last column runs LayT itself; its H-run bound is the one used here);
+//   * layt_ok holds (the best key and finish() are LayT's; its H-run bound is the one used here);
 //   * tags: Hmax + 2 <= KVB with Hmax = (Smax - Smin) / |ge| + 1 as in layt_ok, and 2 <= P <= PMAX
 //     (P >= 2: the column-0 H keys are gone before the first rebase moves the stored keys);
 //   * scores. Real row i = s - off of slot s (i <= 0: padding, S = 0 there as in row 0). In LayT's
@@ -1224,7 +1224,7 @@ PCABI_HD bool packed_ok(int L, int rpl, const Scoring &s) {
 // biases B in [blo, bhi] keep every shifted key's score inside the 10-bit field, strictly above the
 // -512 sentinel. The 2-bit tie field is static, so there is no tag condition; the slot bounds are
 // shift_range's (the same recurrences in Lay's frame):
-//   * packed_ok holds (the last column and finish() run Lay itself);
+//   * packed_ok holds (the best key and finish() are Lay's);
 //   * 2 <= P <= PSHIFT_PMAX = 512: the frame spans at least |ge| P, so no larger power of two can
 //     fit the 1023 values of the field;
 //   * a key of slot s is stored or used at phases -1 (after a rebase) .. P - 1: its shifted score
@@ -1558,9 +1558,9 @@ PCABI_HD Result align_lane_packed(ReadFn &rd, int n, const TabFn &tabfn, int L, 
 // launches of the affine buckets of <= 32 rows whose adapters all pass shift_ok. The inner columns
 // run in the frame -- per cell 4 full-rate VALU ops (V open, G, the next row's diagonal, the tag
 // mask) and 3 maxes, against LayT's 6 + 3; the frame's constants change once per column and are
-// uniform -- and their row-L scout keeps the best key in LayT's frame. Before the last column the
-// stored keys are taken back to LayT keys, and LanePacked<.., LayT>'s last column and finish()
-// run unchanged (their table rows are the frame's substitution keys less a constant, ShiftRow).
+// uniform -- and their row-L scout keeps the best key in LayT's frame. The last column runs in the
+// frame too (LaneShift::last_column): the same cell, one end-cell candidate per row taken to LayT's
+// frame, and Best read off the surviving key; then finish().
 // Same scores and the same winner in every max as LayT, so the results are identical.
 // align_lane_shift4<RPL> is the same core for waves whose windows all have one length: four inner
 // columns per pass over the tile layout's dwords.
@@ -1575,26 +1575,16 @@ PCABI_HD int32_t sub_key_shift(int s, int c, const AdpFn &adp, int off, const Sc
     return (c == adp(s)) ? (Y::sc(sc.ma - sc.go - sc.ge) + Y::TD_K + Y::INC_M)
                          : (Y::sc(sc.mi - sc.go - sc.ge) + Y::TD_K + Y::INC_D);
 }
-// A row of the frame's table read as LayT's: sub_key<LayT> = sub_key_shift + d for every slot and
-// code, d = sc(ge) + ((127 - TDS) << TB_SH).
-template <typename TabRow>
-struct ShiftRow {
-    TabRow t;
-    int32_t d;
-    PCABI_HD int32_t operator()(int s) const { return addw(t(s), d); }
-    PCABI_HD void quad(int q, int32_t *dst) const {
-        t.quad(q, dst);
-        for (int k = 0; k < 4; ++k) dst[k] = addw(dst[k], d);
-    }
-};
 }  // namespace pk
 
 template <int RPL, int PD = PCABI_TAB_PD>
 struct LaneShift {
     using Y = pk::LayS<RPL>;
-    LanePacked<RPL, true, pk::LayT<RPL>, PD> st;   // G, HK, bkey, bj: the frame's keys until to_layt()
+    LanePacked<RPL, true, pk::LayT<RPL>, PD> st;   // G, HK: the frame's keys; bkey, bj: the scout's (LayT's frame)
     int32_t kgo;     // sc(OPEN) + (A(jj) << TB_SH): S key (tag cleared) -> stored G of this column
     int32_t ftop;    // sc(f(0, jj)): uniform
+    int32_t f0;      // sc(f(0, 0)) = sc(-B)
+    int32_t kgo0;    // kgo of phase 0
     int32_t k_e;     // sc(|ge|)
     int32_t k_eR;    // sc(|ge| RPL)
     int32_t k_rb;    // a rebase's score part: sc(ge P)
@@ -1612,15 +1602,16 @@ struct LaneShift {
         k_e = Y::sc(-sc.ge);
         k_eR = Y::sc(-sc.ge * RPL);
         k_rb = Y::sc(sc.ge * P);
+        f0 = Y::sc(-B);
+        kgo0 = Y::sc(sc.go - sc.ge) + ((P - 1) << Y::TB_SH);
         ftop = Y::sc(-sc.ge * j0 - B);
-        kgo = Y::sc(sc.go - sc.ge) + ((P - 1 - j0) << Y::TB_SH);
+        kgo = kgo0 - j0 * Y::TAG1;
         int32_t fs = addw(ftop, kgo);              // sc(f(s, j0) + OPEN), tag A(j0)
 #pragma unroll
         for (int s = 1; s <= RPL; ++s) {
             fs = addw(fs, k_e);
             st.G[s] = addw(Y::start(off - s), fs);   // S(s, 0) = 0; padded (s, 0) reaches real (0, off - s)
-            // H(s, 0) = neg_score, tag A(j0) + 1 (a run just opened: to_layt() gives LayT's column-0
-            // key back when the window has one column): it loses to G in column 1
+            // H(s, 0) = neg_score, tag A(j0) + 1 (a run just opened): it loses to G in column 1
             st.HK[s] = addw(fs, Y::sc(-1) + Y::TAG1);
         }
         st.bkey = Y::start(-L);                    // the (L, 0) seed, LayT's frame
@@ -1700,46 +1691,85 @@ struct LaneShift {
         st.bj = upd ? j : st.bj;
     }
 
-    // The stored keys of phase jj as LayT keys: the score less f(s, jj), G's gap open go instead of
-    // OPEN and its tag cleared, the H tag less A(jj) + 1 (0 = just opened, e after e extends).
-    PCABI_HD void to_layt(const Scoring &sc) {
+    // The last column n at phase jj (after advance() / step()), in the frame: the inner cell, and
+    // every slot's end-cell candidate offered to the scout's key in increasing row order, slot RPL
+    // (row L) last, with the reference's strict '>'. The mirror image of column_tail's argument
+    // makes LanePacked::column<.., true>'s run bookkeeping dead here (go, ge < 0; the held score
+    // is >= 0 from the (L, 0) seed):
+    //   * V never wins an update. V(i, n) = max over k < i of S(k, n) + go + (i - k - 1) ge <
+    //     max over k < i of S(k, n), and every such S(k, n) was offered before row i in this
+    //     column, or is row 0's or a padding slot's 0: V(i, n) < the held score. So the corrected
+    //     state is H or S, and a winner's trailing V run and its predecessor flag are 0.
+    //   * At (L, n) H cannot win either (column_tail: every S(L, j') was offered by the scout), so
+    //     no trailing H run is tracked; below row L a last-column H winner reports trail 0 as the
+    //     V-less Best of LanePacked does.
+    // One candidate per row: corr = max(hn, sn & ~TAGM). H tags are >= A(jj) + 1 > 0, so H wins a
+    // score tie against the tag-cleared S (H over D on equal scores); a higher S score wins with
+    // S's own attributes. The candidate goes to LayT's frame (the score less f(s, jj), a per-row
+    // constant, uniform where the wave's windows share a length), the compare reads the score bytes,
+    // and an update keeps the key and the slot. Best comes from the surviving key: a non-zero tag is H for a last-column winner and V
+    // for the scout's (materialize()). Then finish().
+    template <typename TabRow>
+    PCABI_HD Result last_column(const TabRow &tab, const int n, const int L) {
         using pk::addw;
         using pk::negw;
-        const int32_t tagA = kgo - Y::sc(sc.go - sc.ge);        // A(jj) << TB_SH
-        int32_t cg = addw(negw(addw(ftop, kgo)), Y::sc(sc.go));
-        int32_t ch = negw(addw(ftop, tagA + Y::TAG1));
+        const int off = RPL - L;
+        // the phase's constants from jj alone (== ftop, kgo): where the windows of a wave end at
+        // different columns they are per-lane values, and the inner loop then copies out jj only
+        const int32_t ft = addw(f0, (int32_t)((uint32_t)jj * (uint32_t)k_e));
+        const int32_t kgj = kgo0 - jj * Y::TAG1;
+        const int32_t kg = vreg(kgj);
+        const int32_t top = addw(ft, kgj);
+        int32_t gup = addw(Y::start(n + off), top);
+        int32_t vup = Y::SENT;
+        int32_t diag = addw(addw(Y::start(n - 1 + off), top), Y::TAG1 - k_e);
+        constexpr int NQ = RPL / 4;
+        int32_t t[RPL + 2];
+        if (PD > 0) {
+#pragma unroll
+            for (int q = 0; q <= PD && q < NQ; ++q) tab.quad(q, t + 4 * q + 1);
+        }
+        diag += (PD > 0 ? t[1] : tab(1));
+        int32_t bkey = st.bkey;
+        int brow = 0;                              // the slot that updated last; 0: the scout's key stands
+        int32_t un = negw(ft);                     // -sc(f(s, jj))
 #pragma unroll
         for (int s = 1; s <= RPL; ++s) {
-            cg = addw(cg, negw(k_e));
-            ch = addw(ch, negw(k_e));
-            st.G[s] = addw(st.G[s], cg);
-            st.HK[s] = addw(st.HK[s], ch);
+            if (PD > 0 && (s & 3) == 1) {
+                const int q = (s - 1) / 4 + PD + 1;
+                if (q < NQ) tab.quad(q, t + 4 * q + 1);
+            }
+            int32_t diag_nx = 0;
+            if (s < RPL) diag_nx = st.G[s] + (PD > 0 ? t[s + 1] : tab(s + 1));
+            const int32_t hn = std::max(st.HK[s], st.G[s]);
+            const int32_t vo = gup + Y::kv(s);
+            const int32_t vn = std::max(vup, vo);
+            const int32_t sn = max3i(diag, vn, hn);
+            const int32_t s0 = sn & ~Y::TAGM;
+            un = addw(un, negw(k_e));
+            const int32_t corr = addw(std::max(hn, s0), un);
+            const bool upd = Y::score(corr) > Y::score(bkey);
+            bkey = upd ? corr : bkey;
+            brow = upd ? s : brow;
+            gup = s0 + kg;
+            vup = vn;
+            diag = diag_nx;
+#if defined(__HIP_DEVICE_COMPILE__)
+            if (PCABI_ROW_FENCE > 0 && (s % (PCABI_ROW_FENCE > 0 ? PCABI_ROW_FENCE : 1)) == 0) __builtin_amdgcn_sched_barrier(0);
+#endif
         }
+        const bool last = brow != 0, tagged = Y::tb(bkey) != 0;
+        Best b;
+        b.score = Y::score(bkey);
+        b.bi = last ? brow - off : L;              // slot RPL is row L
+        b.bj = last ? n : st.bj;
+        b.attr = Y::to_std(Y::attr(bkey), b.bj);
+        b.ltype = last ? (tagged ? LT_H : LT_D) : (st.bj == 0 ? LT_NONE : (tagged ? LT_V : LT_D));
+        b.trail = 0;
+        b.precd = 0;
+        return finish(b, L, n);
     }
 };
-
-// After the inner columns: the stored keys back in LayT's frame, then LayT's last column (its table
-// row tab is the frame's, read less a constant) and finish().
-template <int RPL, int PD, typename TabRow>
-PCABI_HD Result shift_last(LaneShift<RPL, PD> &ls, const TabRow &tab, int n, int L, const Scoring &sc) {
-    using Y = pk::LayS<RPL>;
-    ls.to_layt(sc);
-    auto &st = ls.st;
-    const int32_t neg = Y::sc(pk::neg_score(sc));
-    st.k_ge = vreg(Y::sc(sc.ge));
-    st.k_go = vreg(Y::sc(sc.go));
-    st.k_gev = st.k_geh = 0;
-    st.k_gex = vreg(Y::sc(sc.ge) + Y::TB1);
-    st.k_vo = Y::TB2;
-    st.neg2 = neg | Y::TB2;
-    st.materialize(L);
-    const pk::ShiftRow<TabRow> row{tab, Y::sc(sc.ge) + ((127 - Y::TDS) << Y::TB_SH)};
-    st.template column<decltype(row), true>(row, n, L, RPL - L);
-    Best b;
-    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
-    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
-    return finish(b, L, n);
-}
 
 template <int RPL, int PD = PCABI_TAB_PD, typename ReadFn, typename TabFn>
 PCABI_HD Result align_lane_shift(ReadFn &rd, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
@@ -1754,7 +1784,8 @@ PCABI_HD Result align_lane_shift(ReadFn &rd, int n, const TabFn &tabfn, int L, c
         ls.template column<decltype(tabfn(r))>(tabfn(r), j, off);
         r = rn;
     }
-    return shift_last<RPL, PD>(ls, tabfn(r), n, L, sc);
+    ls.advance();
+    return ls.template last_column<decltype(tabfn(r))>(tabfn(r), n, L);
 }
 
 // The same core for a wave whose windows all hold n columns (k_align's cross mode, run_lane): the
@@ -1793,7 +1824,8 @@ PCABI_HD Result align_lane_shift4(const TileFn &tr, int n, const TabFn &tabfn, i
         ls.advance();
         ls.template column<decltype(tabfn(0))>(tabfn((int)((cur >> (8 * ((j - 1) & 3))) & 0xFFu)), j, off);
     }
-    return shift_last<RPL, PD>(ls, tabfn((int)((cur >> (8 * ((n - 1) & 3))) & 0xFFu)), n, L, sc);
+    ls.advance();
+    return ls.template last_column<decltype(tabfn(0))>(tabfn((int)((cur >> (8 * ((n - 1) & 3))) & 0xFFu)), n, L);
 }
 
 // ==========================================================================================
@@ -1807,8 +1839,8 @@ PCABI_HD Result align_lane_shift4(const TileFn &tr, int n, const TabFn &tabfn, i
 // extend add carries along, and all comparands of one max are keys of the same (s, jj). Per cell 8
 // VALU ops (2 max, 1 max3, 2 or, 1 and, the G add, the next row's diagonal add) against Lay's 10.
 // A rebase (every P columns, uniform) adds ge P to the stored scores and touches nothing else.
-// The inner columns' row-L scout keeps the best key in Lay's frame; before the last column the
-// stored keys go back to Lay keys, and LanePacked<.., Lay>'s last column and finish() run unchanged.
+// The inner columns' row-L scout keeps the best key in Lay's frame; the last column runs in the
+// frame too (LanePShift::last_column) and offers its candidates to that key; then finish().
 // ==========================================================================================
 namespace pk {
 template <int RPL, typename AdpFn>
@@ -1824,9 +1856,10 @@ constexpr int32_t PSENT = (int32_t)0x80000000;   // score -512, below every shif
 template <int RPL, int PD = PCABI_TAB_PD>
 struct LanePShift {
     using Y = pk::Lay<RPL>;
-    LanePacked<RPL, true, Y, PD> st;   // G, HK, bkey, bj: the frame's keys until to_lay()
+    LanePacked<RPL, true, Y, PD> st;   // G, HK: the frame's keys; bkey, bj: the scout's (Lay's frame)
     int32_t kgo;     // sc(OPEN): S key (tie field cleared) -> stored G
     int32_t ftop;    // sc(f(0, jj)): uniform
+    int32_t f0;      // sc(f(0, 0)) = sc(-B)
     int32_t k_e;     // sc(|ge|)
     int32_t k_eR;    // sc(|ge| RPL)
     int32_t k_rb;    // a rebase: sc(ge P)
@@ -1840,7 +1873,7 @@ struct LanePShift {
         k_e = Y::sc(-sc.ge);
         k_eR = Y::sc(-sc.ge * RPL);
         k_rb = Y::sc(sc.ge * P);
-        ftop = Y::sc(-B);
+        f0 = ftop = Y::sc(-B);
         kgo = Y::sc(sc.go - sc.ge);
         // the per-slot chains below run in a VGPR (vreg): as uniform values they would be 2 RPL live SGPRs
         int32_t fs = vreg(addw(ftop, kgo));        // sc(f(s, 0) + OPEN)
@@ -1917,25 +1950,77 @@ struct LanePShift {
         st.bj = upd ? j : st.bj;
     }
 
-    // The stored keys of phase jj as Lay keys: the score less f(s, jj), G's gap open go instead of OPEN.
-    PCABI_HD void to_lay(const Scoring &sc) {
+    // The last column n at phase jj (after advance()), in the frame: LaneShift::last_column with
+    // Lay's static tie field. Stored H carries tb 1 and S with the field cleared tb 0, so
+    // max(hn | TB1, sn & ~TBM) lets H win a score tie; V never wins an update and H never wins at
+    // (L, n) (the argument at LaneShift::last_column), so no run is tracked. The scout's key
+    // carries tb 3 for a V winner, a last-column winner tb 1 for H. The windows of a wave end at
+    // different columns here, so the phase is a per-lane value: it is taken from jj alone (f(0, jj) =
+    // |ge| jj - B, which spares the inner loop a second per-lane copy), and instead of taking every
+    // candidate to Lay's frame the held key moves one |ge| per row with the frame and goes back once,
+    // from slot RPL's frame, after the rows. It stays inside the field: a held score lies in [0, L
+    // best_sub], within slot RPL's own bounds in pshift_range less |ge| (RPL - s) >= 0 above, and
+    // no lower than the open key G of row 0 below.
+    template <typename TabRow>
+    PCABI_HD Result last_column(const TabRow &tab, const int n, const int L) {
         using pk::addw;
         using pk::negw;
-        int32_t ch = vreg(negw(ftop));             // VGPR chains, as in init()
-        int32_t cg = addw(ch, Y::sc(sc.ge));
+        const int off = RPL - L;
+        const int32_t kg = vreg(kgo);
+        const int32_t ft = addw(f0, (int32_t)((uint32_t)jj * (uint32_t)k_e));   // == ftop
+        const int32_t top = addw(ft, kgo);
+        int32_t gup = addw(Y::start(n + off), top);
+        int32_t vup = pk::PSENT;
+        int32_t diag = addw(addw(Y::start(n - 1 + off), top), negw(k_e));
+        constexpr int NQ = RPL / 4;
+        int32_t t[RPL + 2];
+        if (PD > 0) {
+#pragma unroll
+            for (int q = 0; q <= PD && q < NQ; ++q) tab.quad(q, t + 4 * q + 1);
+        }
+        diag = addw(diag, PD > 0 ? t[1] : tab(1));
+        int32_t bkey = addw(st.bkey, ft);          // the scout's key in the frame of slot s
+        int brow = 0;                              // the slot that updated last; 0: the scout's key stands
 #pragma unroll
         for (int s = 1; s <= RPL; ++s) {
-            cg = addw(cg, negw(k_e));
-            ch = addw(ch, negw(k_e));
-            st.G[s] = addw(st.G[s], cg);
-            st.HK[s] = addw(st.HK[s], ch);
+            if (PD > 0 && (s & 3) == 1) {
+                const int q = (s - 1) / 4 + PD + 1;
+                if (q < NQ) tab.quad(q, t + 4 * q + 1);
+            }
+            int32_t diag_nx = 0;
+            if (s < RPL) diag_nx = st.G[s] + (PD > 0 ? t[s + 1] : tab(s + 1));
+            const int32_t hn = std::max(st.HK[s], st.G[s]);
+            const int32_t vn2 = std::max(vup, gup) | Y::TB2;
+            const int32_t sn = max3i(diag, vn2, hn);
+            const int32_t s0 = sn & ~Y::TBM;
+            bkey = addw(bkey, k_e);
+            const int32_t corr = std::max(hn | Y::TB1, s0);
+            const bool upd = corr > (bkey | ((1 << Y::SC_SH) - 1));   // score(corr) > score(bkey)
+            bkey = upd ? corr : bkey;
+            brow = upd ? s : brow;
+            gup = s0 + kg;
+            vup = vn2;
+            diag = diag_nx;
+#if defined(__HIP_DEVICE_COMPILE__)
+            if (PCABI_ROW_FENCE > 0 && (s % (PCABI_ROW_FENCE > 0 ? PCABI_ROW_FENCE : 1)) == 0) __builtin_amdgcn_sched_barrier(0);
+#endif
         }
+        bkey = addw(bkey, negw(addw(ft, k_eR)));   // back to Lay's frame
+        const bool last = brow != 0, tagged = Y::tb(bkey) != 0;
+        Best b;
+        b.score = Y::score(bkey);
+        b.bi = last ? brow - off : L;              // slot RPL is row L
+        b.bj = last ? n : st.bj;
+        b.attr = Y::to_std(Y::attr(bkey), b.bj);
+        b.ltype = last ? (tagged ? LT_H : LT_D) : (st.bj == 0 ? LT_NONE : (tagged ? LT_V : LT_D));
+        b.trail = 0;
+        b.precd = 0;
+        return finish(b, L, n);
     }
 };
 
 template <int RPL, int PD = PCABI_TAB_PD, typename ReadFn, typename TabFn>
 PCABI_HD Result align_lane_pshift(ReadFn &rd, int n, const TabFn &tabfn, int L, const Scoring sc, int P, int B) {
-    using Y = pk::Lay<RPL>;
     LanePShift<RPL, PD> ls;
     const int off = RPL - L;
     ls.init(L, sc, P, B);
@@ -1947,25 +2032,8 @@ PCABI_HD Result align_lane_pshift(ReadFn &rd, int n, const TabFn &tabfn, int L, 
         ls.template column<decltype(tabfn(r))>(tabfn(r), j, off);
         r = rn;
     }
-    // the stored keys back in Lay's frame, then Lay's last column (its table row is the frame's,
-    // read less a constant: sub_key<Lay> = sub_key_pshift + sc(ge)) and finish()
-    ls.to_lay(sc);
-    auto &st = ls.st;
-    // one column: its adds may read SGPRs (no vreg), which keeps two VGPRs free where the 64-row
-    // bucket's register count peaks
-    st.k_ge = Y::sc(sc.ge);
-    st.k_go = Y::sc(sc.go);
-    st.k_gev = st.k_geh = 0;
-    st.k_gex = st.k_ge;
-    st.k_vo = 0;
-    st.neg2 = Y::sc(pk::neg_score(sc)) | Y::TB2;
-    st.materialize(L);
-    const pk::ShiftRow<decltype(tabfn(r))> row{tabfn(r), Y::sc(sc.ge)};
-    st.template column<decltype(row), true>(row, n, L, off);
-    Best b;
-    b.score = st.bscore; b.bi = st.bi; b.bj = st.bj; b.attr = Y::to_std(st.battr, st.bj);
-    b.ltype = st.blt; b.trail = st.btrail; b.precd = st.bprec;
-    return finish(b, L, n);
+    ls.advance();
+    return ls.template last_column<decltype(tabfn(r))>(tabfn(r), n, L);
 }
 
 // Long buckets: pass 0 (c, nD) and pass 1 (m) over the same window (two readers, two tables);
