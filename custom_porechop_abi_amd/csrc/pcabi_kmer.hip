@@ -9,14 +9,25 @@
 //                           error level it is found at. A sequence whose best substring is at edit
 //                           distance d <= 2 is reported at d, d+1, ..., 2 errors, so the k-mer's
 //                           count is sum over sequences of (3 - d) for d <= 2 (checked against the
-//                           reference binary on every k-mer of its outputs: tests/golden/g5_kmer).
-// Kernels (HBM / integer work, no MFMA):
+//                           reference binary on every k-mer of its outputs: tests/golden/g5_kmer and,
+//                           for k 4 .. 32, g5_kmer_edge). Below k = 4 the reference crashes in
+//                           errorCount after writing its exact file, so there is no reference answer;
+//                           the entry points keep answering by the 3 - d rule there.
+// Kernels (HBM / integer work, no MFMA; their arithmetic is pcabi_kmer.h, which the tests' host model
+// tests/native/kmer_model.cpp runs on the CPU):
 //   k_kmer_keys   one block per sequence, one lane per position: 2-bit key (first base in the
-//                 top bits, dna2int :55-62) or the sentinel ~0 for a skipped position;
+//                 top bits, dna2int :55-62) or the sentinel ~0 for a skipped position, and at
+//                 k = 32 the number of skipped positions. There the sentinel is also the value of the 32-mer
+//                 TTT...T (which a low-complexity threshold above 15.5 lets through): both end up in
+//                 the last run, and pcabi_kmer_top_host takes the skipped positions off its count
+//                 before either output mode or the sort by count reads it. Below k = 32 the
+//                 sentinel has bits above the key's 2k and the run is dropped as before;
 //   hipcub radix sort + run-length encode -> (k-mer, count);
 //   k_kmer_approx one lane per k-mer, the block's sequences walked with wave-uniform bases:
 //                 Myers' bit-vector edit distance with a free text start (pattern <= 32 bases in
 //                 one register), the minimum over text ends, summed per k-mer.
+// Tests: tests/test_gpu_kmer.py (the three entry points on crafted cases, tests/kmer_cases.py),
+// tests/test_kmer_core_cpu.py (pcabi_kmer.h on the host), tests/test_kmer.py (the driver on G5 / G5-edge).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -25,6 +36,7 @@
 #include <vector>
 
 #include "../../include/pcabi.h"
+#include "pcabi_kmer.h"
 
 namespace pcabi_internal {
 int fail(int code, const std::string &msg);
@@ -39,99 +51,52 @@ using pcabi_internal::fail;
 
 namespace {
 
-constexpr uint64_t kSkip = ~0ull;
+using pcabi_kmer::kSeqPerBlock;
+using pcabi_kmer::kSkip;
 
-// haveLowComplexity (approx_counter.cpp:214-234): counts[16] of the k-1 dimers, sum of
-// v (v - 1) over them == twice the number of equal dimer pairs; s = sum / float(2 (k - 2)).
-__device__ __forceinline__ bool low_complexity(uint64_t kmer, int k, float thr) {
-    uint32_t pairs = 0;
-    for (int i = 0; i < k - 1; ++i) {
-        const uint32_t a = (uint32_t)(kmer >> (2 * i)) & 15u;
-        for (int j = i + 1; j < k - 1; ++j) pairs += ((uint32_t)(kmer >> (2 * j)) & 15u) == a;
-    }
-    const float s = (float)(2u * pairs) / (float)(2 * (k - 2));
-    return s >= thr;
-}
-
+// One block per sequence, one lane per position. At k = 32 n_skipped receives the positions stored as
+// kSkip (at most one atomic a block): the host needs it to tell them from the 32-mer TTT...T.
 __global__ __launch_bounds__(256) void k_kmer_keys(const uint8_t *codes, const int64_t *seq_off, const int32_t *seq_len,
                                                    const int64_t *key_off, int k, float thr, const uint64_t *forb,
-                                                   int64_t n_forb, uint64_t *keys) {
+                                                   int64_t n_forb, uint64_t *keys, unsigned long long *n_skipped) {
+    __shared__ uint32_t block_skipped;
+    const bool count = k == 32;
+    if (count) {
+        if (threadIdx.x == 0) block_skipped = 0;
+        __syncthreads();
+    }
     const int64_t s = blockIdx.x;
     const int n = seq_len[s];
     const int n_pos = n - k + 1;
     const uint8_t *c = codes + seq_off[s];
+    uint32_t mine = 0;
     for (int p = threadIdx.x; p < n_pos; p += blockDim.x) {
-        uint64_t v = 0;
-        bool dna = true;
-        for (int i = 0; i < k; ++i) {
-            const uint32_t x = c[p + i];
-            dna = dna && x < 4;
-            v = (v << 2) | (x & 3u);
-        }
         uint64_t key = kSkip;
-        if (dna && !low_complexity(v, k, thr)) {
-            int64_t lo = 0, hi = n_forb;   // isForbiddenKmer: sorted set lookup
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (forb[mid] < v) lo = mid + 1;
-                else hi = mid;
-            }
-            if (!(lo < n_forb && forb[lo] == v)) key = v;
-        }
+        if (!pcabi_kmer::window_key(c + p, k, thr, forb, n_forb, &key)) ++mine;
         keys[key_off[s] + p] = key;
     }
+    if (!count) return;
+    if (mine) atomicAdd(&block_skipped, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_skipped) atomicAdd(n_skipped, (unsigned long long)block_skipped);
 }
 
 // One wave per block: lane = k-mer (blockIdx.y picks a group of 64), the block walks
 // kSeqPerBlock sequences whose bases are wave-uniform (scalar loads, no per-lane gather).
 // Myers (1999) with D[0][j] = 0 (free text start): the score tracked is D[k][j]; the minimum over
-// j is the best substring's edit distance.
-constexpr int kSeqPerBlock = 32;
-
+// j is the best substring's edit distance (pcabi_kmer.h best_distance).
 __global__ __launch_bounds__(64) void k_kmer_approx(const uint8_t *codes, const int64_t *seq_off,
                                                     const int32_t *seq_len, int64_t n_seq, const uint64_t *kmers,
                                                     int64_t n_kmers, int k, unsigned long long *counts) {
     const int64_t q = (int64_t)blockIdx.y * 64 + threadIdx.x;
-    const uint64_t km = q < n_kmers ? kmers[q] : 0;
-    uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-    for (int i = 0; i < k; ++i) {                     // pattern base i = bits of position k-1-i
-        const uint32_t b = (uint32_t)(km >> (2 * (k - 1 - i))) & 3u;
-        const uint32_t bit = 1u << i;
-        p0 |= b == 0 ? bit : 0u;
-        p1 |= b == 1 ? bit : 0u;
-        p2 |= b == 2 ? bit : 0u;
-        p3 |= b == 3 ? bit : 0u;
-    }
-    const uint32_t mask = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const uint32_t high = 1u << (k - 1);
+    const pcabi_kmer::Masks m = pcabi_kmer::pattern_masks(q < n_kmers ? kmers[q] : 0, k);
     unsigned long long acc = 0;
     const int64_t s0 = (int64_t)blockIdx.x * kSeqPerBlock;
     const int64_t s1 = s0 + kSeqPerBlock < n_seq ? s0 + kSeqPerBlock : n_seq;
     for (int64_t s = s0; s < s1; ++s) {
         // sequences start 4-aligned (approx_counter.sample_sequences packs them): dword loads of
         // wave-uniform addresses, four bases each
-        const uint32_t *c = reinterpret_cast<const uint32_t *>(codes + seq_off[s]);
-        const int n = seq_len[s];
-        uint32_t pv = mask, mv = 0;
-        int score = k, best = k;
-        for (int j0 = 0; j0 < n; j0 += 4) {
-            const uint32_t w = c[j0 >> 2];
-            const int nb = n - j0 < 4 ? n - j0 : 4;
-            for (int b = 0; b < nb; ++b) {
-                const uint32_t x = (w >> (8 * b)) & 0xFFu;   // wave-uniform
-                const uint32_t eq = x == 0 ? p0 : (x == 1 ? p1 : (x == 2 ? p2 : (x == 3 ? p3 : 0u)));
-                const uint32_t xv = eq | mv;
-                const uint32_t xh = ((((eq & pv) + pv) & mask) ^ pv) | eq;
-                uint32_t ph = mv | (~(xh | pv) & mask);
-                uint32_t mh = pv & xh;
-                score += (ph & high) ? 1 : ((mh & high) ? -1 : 0);
-                ph = (ph << 1) & mask;
-                mh = (mh << 1) & mask;
-                pv = mh | (~(xv | ph) & mask);
-                mv = ph & xv;
-                best = score < best ? score : best;
-            }
-        }
+        const int best = pcabi_kmer::best_distance(m, k, reinterpret_cast<const uint32_t *>(codes + seq_off[s]), seq_len[s]);
         acc += best <= 2 ? (unsigned long long)(3 - best) : 0ull;
     }
     if (q < n_kmers && acc) atomicAdd(&counts[q], acc);
@@ -191,6 +156,7 @@ int64_t pcabi_kmer_top_host(int device, const uint8_t *codes, int64_t codes_len,
     uint64_t *d_forb, *d_keys, *d_sorted, *d_unique;
     uint32_t *d_counts;
     int32_t *d_nruns;
+    unsigned long long *d_nskip;
     if (int rc = m.alloc(&d_codes, (size_t)codes_len)) return rc;
     if (int rc = m.alloc(&d_off, (size_t)n_seq)) return rc;
     if (int rc = m.alloc(&d_len, (size_t)n_seq)) return rc;
@@ -200,17 +166,20 @@ int64_t pcabi_kmer_top_host(int device, const uint8_t *codes, int64_t codes_len,
     if (int rc = m.alloc(&d_sorted, (size_t)n_keys)) return rc;
     if (int rc = m.alloc(&d_unique, (size_t)n_keys)) return rc;
     if (int rc = m.alloc(&d_counts, (size_t)n_keys)) return rc;
-    if (int rc = m.alloc(&d_nruns, 1)) return rc;
+    if (int rc = m.alloc(&d_nskip, 2)) return rc;   // the skipped positions, then the number of runs
+    d_nruns = reinterpret_cast<int32_t *>(d_nskip + 1);
+    if (k == 32) KM_TRY(hipMemset(d_nskip, 0, sizeof(unsigned long long)));
     KM_TRY(hipMemcpy(d_codes, codes, (size_t)codes_len, hipMemcpyHostToDevice));
     KM_TRY(hipMemcpy(d_off, seq_off, sizeof(int64_t) * n_seq, hipMemcpyHostToDevice));
     KM_TRY(hipMemcpy(d_len, seq_len, sizeof(int32_t) * n_seq, hipMemcpyHostToDevice));
     KM_TRY(hipMemcpy(d_koff, key_off.data(), sizeof(int64_t) * (n_seq + 1), hipMemcpyHostToDevice));
     if (n_forbidden) KM_TRY(hipMemcpy(d_forb, forbidden_sorted, sizeof(uint64_t) * n_forbidden, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_kmer_keys, dim3((unsigned)n_seq), dim3(128), 0, 0, d_codes, d_off, d_len, d_koff, k,
-                       lc_threshold, d_forb, n_forbidden, d_keys);
+                       lc_threshold, d_forb, n_forbidden, d_keys, d_nskip);
     KM_TRY(hipGetLastError());
     size_t tmp_sort = 0, tmp_rle = 0;
-    // keys use 2k bits; the sentinel ~0 has bit 2k set, so it sorts last
+    // keys use 2k bits; below k = 32 the sentinel ~0 has bit 2k set, so it sorts last (at k = 32 it is
+    // the largest key)
     const int end_bit = 2 * k < 64 ? 2 * k + 1 : 64;
     KM_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_sort, d_keys, d_sorted, (int)n_keys, 0, end_bit));
     KM_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, tmp_rle, d_sorted, d_unique, d_counts, d_nruns, (int)n_keys));
@@ -223,7 +192,20 @@ int64_t pcabi_kmer_top_host(int device, const uint8_t *codes, int64_t codes_len,
     uint64_t last = 0;
     if (nruns > 0) KM_TRY(hipMemcpy(&last, d_unique + nruns - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
     int64_t n_unique = nruns;
-    if (nruns > 0 && (last == kSkip || (2 * k < 64 && (last >> (2 * k)) != 0))) --n_unique;   // the skipped positions
+    if (nruns > 0 && k == 32 && last == kSkip) {
+        // the last run holds the skipped positions and the 32-mer TTT...T alike: what the kernel did
+        // not count as skipped is the k-mer's count, put back on the device for both output modes
+        unsigned long long n_skip = 0;
+        uint32_t run = 0;
+        KM_TRY(hipMemcpy(&n_skip, d_nskip, sizeof(n_skip), hipMemcpyDeviceToHost));
+        KM_TRY(hipMemcpy(&run, d_counts + nruns - 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (n_skip > run) return fail(PCABI_E_DEVICE, "k-mer count: more skipped positions than the last run holds");
+        run -= (uint32_t)n_skip;
+        if (run == 0) --n_unique;
+        else KM_TRY(hipMemcpy(d_counts + nruns - 1, &run, sizeof(uint32_t), hipMemcpyHostToDevice));
+    } else if (nruns > 0 && k < 32 && (last >> (2 * k)) != 0) {
+        --n_unique;   // the skipped positions
+    }
     if (top < 0) {                                     // every k-mer, ascending
         if (n_unique > cap) return n_unique;
         if (n_unique) {

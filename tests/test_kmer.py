@@ -5,7 +5,12 @@ sampled so the reference is deterministic):
   * not gpu: the driver (config / options, sampling, CompareCount ordering, DUST complexity,
     threshold scaling, forbidden and solid k-mers, multi-run names, the skip-end quirk, export)
     with the CPU restatement of the two counting steps (tests/kmer_oracle.py);
-  * gpu    : the same with the HIP kernels (k_kmer_keys + hipcub sort / RLE, k_kmer_approx)."""
+  * gpu    : the same with the HIP kernels (k_kmer_keys + hipcub sort / RLE, k_kmer_approx).
+G5-edge (tests/golden/g5_kmer_edge.json.gz, the cases 'edge0' ..) pins the ends of the k range on a small
+third input: k 4, 5, 8, 11, 21, 24, 31 and 32, the last with a low-complexity threshold that lets the
+32-mer TTT...T through -- its value is the one skipped positions are stored as. Below k = 4 the reference
+program crashes in errorCount, so no case pins the approximate counts there. The kernels themselves are
+tested case by case in tests/test_gpu_kmer.py and tests/test_kmer_core_cpu.py."""
 import gzip
 import json
 import os
@@ -16,6 +21,9 @@ import pytest
 from tests import golden_lib
 
 G5 = json.load(gzip.open(os.path.join(golden_lib.GOLDEN, 'g5_kmer.json.gz'), 'rt'))['cases']
+EDGE = json.load(gzip.open(os.path.join(golden_lib.GOLDEN, 'g5_kmer_edge.json.gz'), 'rt'))['cases']
+CASES = dict([(i, c) for i, c in enumerate(G5)] + [('edge%d' % i, c) for i, c in enumerate(EDGE)])
+EDGE_CPU = [i for i in CASES if str(i).startswith('edge')]   # small enough for the CPU restatement, all of them
 
 
 def _run_case(case, tmp_path):
@@ -42,23 +50,23 @@ def _compare(case, got):
             assert got[fn] == exp, fn
 
 
-@pytest.mark.parametrize('idx', range(len(G5)))
+@pytest.mark.parametrize('idx', list(range(len(G5))) + EDGE_CPU)
 def test_counter_driver_with_cpu_restatement(idx, tmp_path, monkeypatch):
     from custom_porechop_abi_amd import approx_counter as AC
     from tests import kmer_oracle
     monkeypatch.setattr(AC, 'count_kmers', kmer_oracle.count_kmers)
     monkeypatch.setattr(AC, 'count_kmers_top', kmer_oracle.count_kmers_top)
     monkeypatch.setattr(AC, 'error_count', kmer_oracle.error_count)
-    case = G5[idx]
-    if idx not in (0, 4, 5, 7):
+    case = CASES[idx]
+    if idx in (1, 2, 3, 6):
         pytest.skip('CPU restatement: a subset of the cases keeps the CPU suite short')
     _compare(case, _run_case(case, tmp_path))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('idx', range(len(G5)))
+@pytest.mark.parametrize('idx', list(CASES))
 def test_counter_on_gpu_matches_reference(gpu_lib, idx, tmp_path):
-    case = G5[idx]
+    case = CASES[idx]
     _compare(case, _run_case(case, tmp_path))
 
 
