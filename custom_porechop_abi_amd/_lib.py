@@ -192,6 +192,12 @@ def lib():
         'pcabi_qual_filter_host': ([c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p], c_int),
         'pcabi_qual_error_table': ([c_p], None),
         'pcabi_qual_last_times': ([c_int, c_int, c_p, c_p], None),
+        'pcabi_qual_pieces_bound': ([c_p, c_p, c_i64, c_p, c_p], c_int),
+        'pcabi_qual_pieces_scratch_bytes': ([c_i64, c_i64, c_i64, c_i64], c_i64),
+        'pcabi_qual_pieces_dev': ([c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64,
+                                   c_p], c_int),
+        'pcabi_qual_pieces_host': ([c_int, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64], c_int),
+        'pcabi_qual_pieces_last_times': ([c_int, c_int, c_p, c_p], None),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(L, name)
@@ -243,7 +249,8 @@ def exported_symbols():
             'pcabi_reads_write_tags', 'pcabi_auxparse_plan', 'pcabi_auxparse_write', 'pcabi_auxparse_counts',
             'pcabi_auxparse_last_times', 'pcabi_fastx_header_tags', 'pcabi_qual_seg_bound',
             'pcabi_qual_scratch_bytes', 'pcabi_qual_filter_dev', 'pcabi_qual_filter_host', 'pcabi_qual_error_table',
-            'pcabi_qual_last_times']
+            'pcabi_qual_last_times', 'pcabi_qual_pieces_bound', 'pcabi_qual_pieces_scratch_bytes', 'pcabi_qual_pieces_dev',
+            'pcabi_qual_pieces_host', 'pcabi_qual_pieces_last_times']
 
 
 class CrossRegion(ctypes.Structure):

@@ -37,6 +37,7 @@ constexpr int kMaxWindow = 64;                      // one window start a lane
 constexpr int kMaxQ = 93;
 constexpr int64_t kMaxBlob = (int64_t)1 << 31;      // bytes a batch may hold
 constexpr uint64_t kErrOne = (uint64_t)1 << 32;     // error probability 1: max_mean_err's "off"
+constexpr int32_t kFail = PCABI_QUAL_TOO_SHORT | PCABI_QUAL_TOO_LONG | PCABI_QUAL_LOW_QUALITY;   // a read, or a piece, fails
 
 // E[q] = round(2^32 * 10^(-q / 10)), q = 0..93 (tests/qual_ref.py recomputes it)
 #define PCABI_QUAL_ERR_TABLE                                                                                        \

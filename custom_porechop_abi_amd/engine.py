@@ -1180,3 +1180,55 @@ def quality_filter(qual, span_off, span_len, window=0, min_window_q=0.0, min_len
                                       span_off.size, _ptr(opts), _ptr(out))
     check(int(rc), 'pcabi_qual_filter_host')
     return out
+
+
+# include/pcabi.h pcabi_qual_piece
+QUAL_PIECE = np.dtype([('read', np.int64), ('begin', np.int64), ('end', np.int64), ('q', QUAL_READ)])
+assert QUAL_PIECE.itemsize == 56
+
+
+def quality_pieces_bound(span_len, cut_off):
+    """The host-side bounds of the piece stage (pcabi_qual_pieces_bound): (pieces, segments)."""
+    span_len = np.ascontiguousarray(span_len, np.int32)
+    cut_off = np.ascontiguousarray(cut_off, np.int64)
+    if cut_off.ndim != 1 or cut_off.size != span_len.size + 1:
+        raise ValueError('quality_pieces_bound: cut_off holds one entry more than there are reads')
+    out = np.zeros(2, np.int64)
+    check(int(lib().pcabi_qual_pieces_bound(_ptr(span_len), _ptr(cut_off), span_len.size, out[0:].ctypes.data, out[1:].ctypes.data)),
+          'pcabi_qual_pieces_bound')
+    return int(out[0]), int(out[1])
+
+
+def quality_filter_pieces(qual, span_off, span_len, cut_off, cuts, window=0, min_window_q=0.0, min_length=0, max_length=0,
+                          min_mean_q=0.0, device=0, opts=None):
+    """The split reads of a batch judged piece by piece (pcabi_qual_pieces_host; the rule: include/pcabi.h).
+    qual / span_off / span_len as quality_filter takes them (span_len: the trimmed lengths); cut_off / cuts:
+    the reads' ranges in the writers' layout (int64 [n + 1], int64 [2 * cut_off[n]]). Every piece the
+    writers would cut a split read into is cropped and tested like a read of its own. On GPU `device`, or
+    with the host build when device is None or < 0. Returns (cut_off', cuts', pieces, piece_off): the cut
+    layout that makes every writer emit exactly the cropped, passing pieces; a QUAL_PIECE array (read,
+    begin, end, q: a QUAL_READ record); piece_off int64 [n + 1], read r's pieces being
+    pieces[piece_off[r]:piece_off[r + 1]]."""
+    qual = _bytes_arg(qual)
+    span_off = np.ascontiguousarray(span_off, np.int64)
+    span_len = np.ascontiguousarray(span_len, np.int32)
+    cut_off = np.ascontiguousarray(cut_off, np.int64)
+    cuts = np.ascontiguousarray(cuts, np.int64).reshape(-1)
+    n = span_off.size
+    if span_off.shape != span_len.shape or span_off.ndim != 1:
+        raise ValueError('quality_filter_pieces: span_off and span_len are one-dimensional and equally long')
+    if cut_off.ndim != 1 or cut_off.size != n + 1 or int(cut_off[-1]) * 2 != cuts.size:
+        raise ValueError('quality_filter_pieces: cut_off holds n + 1 entries and cuts two values a range')
+    if opts is None:
+        opts = qual_opts(window, min_window_q, min_length, max_length, min_mean_q)
+    opts = np.ascontiguousarray(opts, QUAL_OPTS)
+    cap, _ = quality_pieces_bound(span_len, cut_off)
+    n_ranges = cuts.size // 2
+    piece_off, cut_off2 = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    pieces, cuts2 = np.zeros(cap, QUAL_PIECE), np.zeros(2 * (n_ranges + 2 * cap), np.int64)
+    rc = lib().pcabi_qual_pieces_host(-1 if device is None else int(device), _ptr(qual), qual.size, _ptr(span_off), _ptr(span_len), n,
+                                      _ptr(cut_off), _ptr(cuts), _ptr(opts), _ptr(piece_off), _ptr(pieces), cap, _ptr(cut_off2),
+                                      _ptr(cuts2), n_ranges + 2 * cap)
+    check(int(rc), 'pcabi_qual_pieces_host')
+    n_pieces = int(piece_off[n])
+    return cut_off2, cuts2[:2 * int(cut_off2[n])].copy(), pieces[:n_pieces].copy(), piece_off

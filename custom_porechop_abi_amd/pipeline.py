@@ -24,8 +24,8 @@ import numpy as np
 
 from . import misc
 from ._lib import check, cross_regions, lib
-from .engine import QUAL_FAIL, QUAL_LOW_QUALITY, QUAL_NO_QUALITIES, QUAL_READ, QUAL_TOO_LONG, QUAL_TOO_SHORT, encode_adapters, \
-    middle_cuts, qual_opts
+from .engine import QUAL_FAIL, QUAL_LOW_QUALITY, QUAL_NO_QUALITIES, QUAL_PIECE, QUAL_READ, QUAL_TOO_LONG, QUAL_TOO_SHORT, \
+    encode_adapters, middle_cuts, qual_opts
 from .porechop_abi import middle_adapter_list
 
 VP = ctypes.c_void_p
@@ -87,9 +87,19 @@ class FileTrimmer(object):
     kept span and clear the read's keep bit. A read without qualities is not cropped and passes the
     quality test. The fork's start-and-end filter still goes by the adapter trims; with
     filter_reads=False keep is the pass mask. The filter sees the kept span with its middle adapters:
-    split pieces are not filtered one by one. The barcode bins go through the same trims and keep mask;
+    split pieces are not filtered one by one unless quality_per_piece is set (below). The barcode bins go through the same trims and keep mask;
     with untrimmed=True their writer ignores the trims, as it does today, so the crop is not visible
-    there while the filter still applies. last_quality holds the last batch's QUAL_READ records."""
+    there while the filter still applies. last_quality holds the last batch's QUAL_READ records.
+
+    quality_per_piece=True (it needs the stage on) judges split reads piece by piece, as a filter run on
+    the written file would: after the middle scan the pieces the writers would cut a split read into are
+    cropped and tested on the device like reads of their own (engine.quality_filter_pieces, the rule:
+    include/pcabi.h), and trim() returns in place of the scan's cuts a cut layout with which every writer,
+    the bins' included, emits exactly the cropped, passing pieces, numbered _1, _2, ... over the pieces
+    written, min_split_read_size applying to the cropped piece. A split read's keep bit no longer takes the
+    whole-read verdict (a read all of whose pieces fail writes nothing); the fork's start-and-end filter
+    and discard_middle are unchanged. last_quality_pieces holds the last batch's QUAL_PIECE records,
+    last_piece_off their offsets per read."""
 
     barcode_dir = None                    # -b off (set by __init__)
     gzip_device = None                    # '.gz' formats through zlib on the host (set by __init__)
@@ -107,6 +117,9 @@ class FileTrimmer(object):
     max_length = 0                        # no read is too long
     min_mean_q = 0.0                      # no read is of too low a quality
     last_quality = None                   # the quality stage's records of the last batch (stage on)
+    quality_per_piece = False             # split reads are judged whole, middle adapters included
+    last_quality_pieces = None            # the piece stage's records of the last batch (quality_per_piece)
+    last_piece_off = None                 # read r's pieces: last_quality_pieces[last_piece_off[r]:last_piece_off[r + 1]]
 
     def __init__(self, matching_sets, scoring_scheme_vals=(3, -6, -5, -2), end_size=150, end_threshold=75.0,
                  extra_end_trim=2, min_trim_size=4, middle_threshold=90.0, extra_middle_trim_good_side=10,
@@ -115,12 +128,15 @@ class FileTrimmer(object):
                  barcode_threshold=75.0, barcode_diff=5.0, require_two_barcodes=False, untrimmed=False,
                  discard_unassigned=False, gzip_on_device=False, gunzip_on_device=False, bgzf=False, keep_tags=False,
                  keep_mods=False, keep_moves=False, gunzip_plain=False, header_tags=False, tags_from_headers=False, quality_window=0,
-                 quality_window_q=0.0, min_length=0, max_length=0, min_mean_q=0.0):
+                 quality_window_q=0.0, min_length=0, max_length=0, min_mean_q=0.0, quality_per_piece=False):
         self.L = L = lib()
         if not 0 <= int(quality_window) <= 64:
             raise ValueError('quality_window is 0 (off) or 1..64')
         self.quality_window, self.quality_window_q = int(quality_window), float(quality_window_q)
         self.min_length, self.max_length, self.min_mean_q = int(min_length), int(max_length), float(min_mean_q)
+        if quality_per_piece and not self._quality_on():
+            raise ValueError('quality_per_piece needs the quality stage on (quality_window, min_length, max_length or min_mean_q)')
+        self.quality_per_piece = bool(quality_per_piece)
         # tags_from_headers: a FASTA / FASTQ input's tags are read from its headers (misc.read_batches
         # tags_from_headers; on the device with gunzip_on_device, else the host build), so every writer,
         # the bins' included, carries them as it carries a BAM input's
@@ -265,6 +281,45 @@ class FileTrimmer(object):
         new_et = np.where(cropped, lens - (a + n - tail), et).astype(np.int32)
         return new_st, new_et, recs
 
+    def _piece_stage(self, batch, lens, trims, d_qual, cut_off, cuts):
+        """The piece stage on the cuts the middle scan found (the qualities are still on the device; the
+        spans are those the whole-read stage's trims leave): -> (cut_off', cuts', pieces, piece_off)."""
+        L, nb = self.L, batch.n
+        a, n = _trimmed_span(lens, trims[0].astype(np.int64), trims[1].astype(np.int64))
+        has_q = np.diff(batch.qual_off) == lens
+        span_off = np.where(has_q, batch.qual_off[:-1] + a, -1).astype(np.int64)
+        span_len = n.astype(np.int32)
+        cut_off = np.ascontiguousarray(cut_off, np.int64)
+        cuts = np.ascontiguousarray(cuts, np.int64).reshape(-1)
+        n_ranges = int(cut_off[-1])
+        opts = qual_opts(self.quality_window, self.quality_window_q, self.min_length, self.max_length, self.min_mean_q)
+        bound = np.zeros(2, np.int64)
+        check(L.pcabi_qual_pieces_bound(span_len.ctypes.data_as(VP), cut_off.ctypes.data_as(VP), nb, bound[0:].ctypes.data_as(VP),
+                                        bound[1:].ctypes.data_as(VP)), 'pcabi_qual_pieces_bound')
+        cap, n_segs = int(bound[0]), int(bound[1])
+        cuts_cap = n_ranges + 2 * cap
+        need = int(L.pcabi_qual_pieces_scratch_bytes(nb, n_ranges, cap, n_segs))
+        if need < 0:
+            check(need, 'pcabi_qual_pieces_scratch_bytes')
+        d_off, d_len = self._h2d('qoff', span_off), self._h2d('qlen', span_len)
+        d_co, d_cu = self._h2d('pcut_off', cut_off), self._h2d('pcuts', cuts)
+        d_po, d_pieces = self._buf('ppiece_off', 8 * (nb + 1)), self._buf('ppieces', QUAL_PIECE.itemsize * cap)
+        d_co2, d_cu2 = self._buf('pcut_off2', 8 * (nb + 1)), self._buf('pcuts2', 16 * cuts_cap)
+        d_scr = self._buf('pscratch', need)
+        check(L.pcabi_qual_pieces_dev(d_qual, batch.qual.size, d_off, d_len, nb, d_co, d_cu, n_ranges, cap, n_segs, opts.ctypes.data_as(VP),
+                                      d_po, d_pieces, d_co2, d_cu2, cuts_cap, d_scr, need, self.stream), 'pcabi_qual_pieces_dev')
+        piece_off, cut_off2 = np.zeros(nb + 1, np.int64), np.zeros(nb + 1, np.int64)
+        pieces, cuts2 = np.zeros(cap, QUAL_PIECE), np.zeros(2 * cuts_cap, np.int64)
+        # the bounds are small next to the batch: everything comes up in one go, the counts trim it
+        for dst, src in ((piece_off, d_po), (cut_off2, d_co2), (pieces, d_pieces), (cuts2, d_cu2)):
+            if dst.nbytes:
+                check(L.pcabi_dev_copy_async(dst.ctypes.data_as(VP), src, dst.nbytes, 1, self.stream), 'd2h')
+        check(L.pcabi_stream_sync(self.stream), 'sync')
+        n_pieces = int(piece_off[nb])
+        if not 0 <= n_pieces <= cap or int(cut_off2[nb]) != n_ranges + 2 * n_pieces:
+            raise RuntimeError('the piece stage returned %d pieces for a bound of %d' % (n_pieces, cap))
+        return cut_off2, cuts2[:2 * int(cut_off2[nb])].copy(), pieces[:n_pieces].copy(), piece_off
+
     def _tick(self, key, t):
         now = time.perf_counter()
         self.times[key] = self.times.get(key, 0.0) + now - t
@@ -291,6 +346,9 @@ class FileTrimmer(object):
         # the qualities cross PCIe beside the alignment
         d_qual = self._h2d('qual', batch.qual) if quality and nb else None
         self.last_quality = np.zeros(0, QUAL_READ) if quality else None
+        per_piece = quality and self.quality_per_piece
+        self.last_quality_pieces = np.zeros(0, QUAL_PIECE) if per_piece else None
+        self.last_piece_off = np.zeros(nb + 1, np.int64) if per_piece else None
         trims = np.zeros((2, nb), np.int32)
         res = [None, None]
         regions = []
@@ -342,12 +400,21 @@ class FileTrimmer(object):
             t = self._tick('quality', t)
         cut_off, cuts, hits = self.middle_scan(batch, trims[0], trims[1], d_codes)
         t = self._tick('middle', t)
+        split = None
+        if per_piece and nb and int(cut_off[-1]) > 0:
+            # the writers' rule: a read with a non-empty range is split; its pieces are judged, not the read
+            nonempty = np.concatenate([[0], np.cumsum(cuts[1::2] > cuts[0::2])])
+            split = nonempty[cut_off[1:]] > nonempty[cut_off[:-1]]
+            cut_off, cuts, self.last_quality_pieces, self.last_piece_off = self._piece_stage(batch, lens, trims, d_qual, cut_off, cuts)
+            t = self._tick('quality_pieces', t)
         keep = None
         if self.filter_reads:
             # the fork's filter: start AND end alignments (a recorded alignment always trims >= 1)
             keep = ((adapter_trims[0] > 0) & (adapter_trims[1] > 0)).astype(np.uint8)
         if quality:
             passed = ((self.last_quality['flags'] & QUAL_FAIL) == 0).astype(np.uint8)
+            if split is not None:
+                passed[split] = 1
             keep = passed if keep is None else keep & passed
         return trims[0], trims[1], cut_off, cuts, hits, keep
 
@@ -412,12 +479,16 @@ class FileTrimmer(object):
         are this thread's waits, 'read' / 'write' the reader's / writer's own busy time (overlapped).
 
         With the quality stage on, counts['quality'] tallies its records: cropped_reads, cropped_bases,
-        too_short, too_long, low_quality, no_qualities."""
+        too_short, too_long, low_quality, no_qualities; with quality_per_piece also pieces, piece_cropped,
+        piece_cropped_bases, piece_too_short, piece_too_long, piece_low_quality over the split reads' pieces."""
         counts = {'reads_in': 0, 'reads_kept': 0}
         quality = None
         if getattr(self, '_quality_on', lambda: False)():
             quality = counts['quality'] = {k: 0 for k in ('cropped_reads', 'cropped_bases', 'too_short', 'too_long', 'low_quality',
                                                          'no_qualities')}
+            if getattr(self, 'quality_per_piece', False):
+                quality.update({k: 0 for k in ('pieces', 'piece_cropped', 'piece_cropped_bases', 'piece_too_short', 'piece_too_long',
+                                               'piece_low_quality')})
         # PCABI_PIPE_TRACE=1: (stage, batch, begin, end) per stage and batch in self.trace (the
         # pipeline's timeline: which stage holds the others up)
         trace = self.trace = [] if os.environ.get('PCABI_PIPE_TRACE') == '1' else None
@@ -546,6 +617,15 @@ class FileTrimmer(object):
                     for key, bit in (('too_short', QUAL_TOO_SHORT), ('too_long', QUAL_TOO_LONG), ('low_quality', QUAL_LOW_QUALITY),
                                      ('no_qualities', QUAL_NO_QUALITIES)):
                         quality[key] += int(((q['flags'] & bit) != 0).sum())
+                    if self.last_quality_pieces is not None:
+                        q = self.last_quality_pieces['q']
+                        crop = q['front'].astype(np.int64) + q['tail']
+                        quality['pieces'] += int(q.size)
+                        quality['piece_cropped'] += int((crop > 0).sum())
+                        quality['piece_cropped_bases'] += int(crop.sum())
+                        for key, bit in (('piece_too_short', QUAL_TOO_SHORT), ('piece_too_long', QUAL_TOO_LONG),
+                                         ('piece_low_quality', QUAL_LOW_QUALITY)):
+                            quality[key] += int(((q['flags'] & bit) != 0).sum())
                 t1 = time.perf_counter()
                 wq.put((k, b, st, et, co, cu, keep, calls))   # the writer drains even after a failure
                 del b

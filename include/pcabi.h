@@ -1368,9 +1368,53 @@ int pcabi_fastx_header_tags(pcabi_fastx *r, int on, int device);
  *       ms[0..3] = milliseconds of k_qual_crop, of k_qual_sum, the wall time of the host build and the
  *       wall time of the device stage behind the uploads (kernels, scan, records back); bytes[0..1] =
  *       the spans' bytes the two kernels were given; all since the last call with reset != 0.
- * Out of scope: per-piece filtering of split reads (the filter sees the kept span, middle adapters
- * included); rewriting dorado's qs tag for a cropped read; fastp's base-by-base trim inside the first
- * good window; windows over 64; sharded runs; qualities kept on the device by the BAM or gunzip readers.
+ * The piece stage (csrc/pcabi_pieces.h; pcabi_qual_pieces_*): the stage above sees a chimeric read as one
+ * span, middle adapters included, while the writers cut it into pieces. This stage judges the pieces.
+ * The pieces of read r, from its trimmed length tl = span_len[r] and its ranges [cuts[2k], cuts[2k + 1])
+ * for k in [cut_off[r], cut_off[r + 1]) (positions of the trimmed sequence, in any order; they may
+ * overlap, nest, repeat, be empty, begin below 0 or end beyond tl): the read is split when at least one
+ * of its ranges is non-empty (end > begin), even if that range lies wholly outside [0, tl) -- the single
+ * piece is then [0, tl); the pieces are the maximal runs of positions of [0, tl) that no non-empty range
+ * covers, ascending; runs of length 0 do not exist; a read that is not split has no pieces (the stage
+ * above has dealt with it). This is the writers' rule (pcabi_reads_write), restated.
+ * Each piece (read, begin, end) is a span of its own, span_off[r] + begin of length end - begin (span_off[r]
+ * < 0 stays < 0: no qualities), cropped, summed and tested by the same kernels with the same options:
+ * one pcabi_qual_read per piece. The result goes to the writers as a new cut layout, cut_off'[r] =
+ * cut_off[r] + 2 * piece_off[r]: read r's ranges as they came, in their order, then two ranges a piece:
+ * [begin, begin + front) and [end - tail, end) for a piece that passes, [begin, end) and the empty [end,
+ * end) for one that fails (TOO_SHORT, TOO_LONG or LOW_QUALITY after its crop). Reads that are not split
+ * keep their ranges and get none added. The writers ignore empty ranges, so with (cut_off', cuts') every
+ * writer emits exactly the cropped, passing pieces, numbered _1, _2, ... over the pieces written, its
+ * min_split_read_size applied to the cropped piece, the MM ML MN mv ts remap following the same cuts.
+ *   pcabi_qual_pieces_bound         : (host) upper bounds nothing is read back for: pieces <= ranges + reads
+ *       with ranges; segments <= the sum of n_segs(span_len) over the reads with ranges + that piece bound.
+ *   pcabi_qual_pieces_scratch_bytes : the scratch pcabi_qual_pieces_dev needs.
+ *   pcabi_qual_pieces_dev           : device pointers on the current device, asynchronous on `stream`, no
+ *       host round trip: k_piece_keys and a 64-bit radix sort order the ranges by (read, begin), so a read
+ *       may have any number of them; k_piece_count, one thread per read, walks them; a device scan gives
+ *       piece_off[n_reads + 1]; k_piece_spans writes the pieces and their spans (the slots up to piece_cap
+ *       become empty spans); k_qual_crop, the segment scan, k_qual_sum and k_qual_finish run over them;
+ *       k_piece_cuts writes cut_off_out[n_reads + 1], cuts_out (cuts_cap ranges, at least n_ranges + 2 *
+ *       piece_cap) and the pieces' records. pieces[0, piece_off[n_reads]) are valid. piece_cap and seg_cap
+ *       must be the values pcabi_qual_pieces_bound gives for this cut_off (ranges + reads with ranges): the
+ *       call sees device pointers and cannot count the reads with ranges, so it can refuse only a
+ *       piece_cap below n_ranges + 1; with a cap between that and the bound the kernels write nothing out
+ *       of bounds but drop the pieces beyond it, and pieces and cuts_out are undefined (piece_off[n_reads]
+ *       > piece_cap tells; pcabi_qual_pieces_host computes the bound itself). Bad options, a blob over
+ *       2^31 bytes, such a piece_cap, a cuts_cap or a scratch buffer that is too small are refused
+ *       (PCABI_E_ARG) before any launch.
+ *   pcabi_qual_pieces_host          : host buffers, uploaded and run as above on `device`; device < 0 runs
+ *       the host build of the same headers (no GPU needed): the enumeration, a sort per read and the cut
+ *       layout on the calling thread, the crop and sums of the piece spans on the io threads. piece_cap / cuts_cap: the room of pieces /
+ *       cuts_out, at least the bound / n_ranges + 2 * piece_cap. cut_off that does not begin at 0 or
+ *       descends, and spans outside the blob, are refused as well.
+ *   pcabi_qual_pieces_last_times    : as pcabi_qual_last_times, for pcabi_qual_pieces_host: ms[0..5] = the
+ *       plan kernels (keys, sort, count, scan, spans), k_qual_crop over the piece spans, k_qual_sum over
+ *       them, k_piece_cuts, the wall time of the host build, the wall time of the device stage behind the
+ *       uploads; bytes[0..3] = what the first four were given.
+ * Out of scope: rewriting dorado's qs tag for a cropped read or piece; sp / pi tags on pieces; running
+ * the middle scan again on cropped pieces; fastp's base-by-base trim inside the first good window;
+ * windows over 64; sharded runs; qualities kept on the device by the BAM or gunzip readers.
  */
 #define PCABI_QUAL_TOO_SHORT 1
 #define PCABI_QUAL_TOO_LONG 2
@@ -1401,6 +1445,24 @@ int pcabi_qual_filter_host(int device, const uint8_t *qual, int64_t qual_n, cons
                            pcabi_qual_read *out);
 void pcabi_qual_error_table(uint64_t *table);
 void pcabi_qual_last_times(int on, int reset, double *ms, int64_t *bytes);
+typedef struct pcabi_qual_piece {
+    int64_t read;       /* the read the piece is of */
+    int64_t begin, end; /* positions of the trimmed sequence */
+    pcabi_qual_read q;  /* over qual[span_off[read] + begin, span_off[read] + end) */
+} pcabi_qual_piece;
+int pcabi_qual_pieces_bound(const int32_t *span_len, const int64_t *cut_off, int64_t n_reads, int64_t *n_pieces,
+                            int64_t *n_segs);
+int64_t pcabi_qual_pieces_scratch_bytes(int64_t n_reads, int64_t n_ranges, int64_t piece_cap, int64_t seg_cap);
+int pcabi_qual_pieces_dev(const uint8_t *qual, int64_t qual_n, const int64_t *span_off, const int32_t *span_len,
+                          int64_t n_reads, const int64_t *cut_off, const int64_t *cuts, int64_t n_ranges,
+                          int64_t piece_cap, int64_t seg_cap, const pcabi_qual_opts *opts, int64_t *piece_off,
+                          pcabi_qual_piece *pieces, int64_t *cut_off_out, int64_t *cuts_out, int64_t cuts_cap,
+                          void *scratch, int64_t scratch_len, void *stream);
+int pcabi_qual_pieces_host(int device, const uint8_t *qual, int64_t qual_n, const int64_t *span_off,
+                           const int32_t *span_len, int64_t n_reads, const int64_t *cut_off, const int64_t *cuts,
+                           const pcabi_qual_opts *opts, int64_t *piece_off, pcabi_qual_piece *pieces,
+                           int64_t piece_cap, int64_t *cut_off_out, int64_t *cuts_out, int64_t cuts_cap);
+void pcabi_qual_pieces_last_times(int on, int reset, double *ms, int64_t *bytes);
 
 #ifdef __cplusplus
 }

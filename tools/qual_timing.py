@@ -13,7 +13,15 @@ The device's records must equal the host build's.
 The whole file. --file-reads reads of bench.py's e2e workload (synth.make_reads, its FASTQ text) through
 FileTrimmer.trim_file, FASTQ to FASTQ, with the stage on (window 10 at 10, min_length 1000, min_mean_q 7)
 and off, as three alternating on / off pairs after one warm-up of each; the range seen is reported.
---file-reads 0 skips it. --device -1 runs the host build alone. Prints one JSON line (and writes it to --out)."""
+--file-reads 0 skips it. --device -1 runs the host build alone. Prints one JSON line (and writes it to --out).
+
+--pieces [--share 0.05,1.0]: the piece stage on the same batch (engine.quality_filter_pieces). In the stated
+share of the reads a middle adapter is planted: one cut range of 120 bases around the read's middle with 30
+bases of Phred 0..4 on either side of it, so each such read gives two pieces that crop. Reported per share
+(medians, from pcabi_qual_pieces_last_times): the plan kernels (keys, sort, count, scan, spans), k_qual_crop
+and k_qual_sum over the piece spans, k_piece_cuts, the wall time of the device stage behind the uploads and
+of the host build; beside them k_qual_crop / k_qual_sum over the whole reads from the same run. The device's
+results must equal the host build's."""
 import argparse
 import ctypes
 import json
@@ -85,6 +93,65 @@ def table_level(L, args):
     return res
 
 
+def piece_times(L, on, reset):
+    ms, nbytes = (ctypes.c_double * 6)(), (ctypes.c_int64 * 4)()
+    L.pcabi_qual_pieces_last_times(int(on), int(reset), ms, nbytes)
+    return [float(x) for x in ms]
+
+
+def plant_cuts(qual, off, ln, share, seed=9):
+    """A middle adapter's cut in `share` of the reads: -> (qual with low qualities beside the cuts, cut_off, cuts)."""
+    rng = np.random.default_rng(seed)
+    qual = qual.copy()
+    hit = rng.random(ln.size) < share if share < 1.0 else np.ones(ln.size, bool)
+    hit &= ln >= 400
+    mid = ln.astype(np.int64) // 2
+    for k in range(30):
+        for at in (off[hit] + mid[hit] - 61 - k, off[hit] + mid[hit] + 60 + k):
+            qual[at] = rng.integers(33, 38, at.size, dtype=np.uint8)
+    cut_off = np.concatenate(([0], np.cumsum(hit))).astype(np.int64)
+    cuts = np.stack([mid[hit] - 60, mid[hit] + 60], axis=1).reshape(-1).astype(np.int64)
+    return qual, cut_off, cuts
+
+
+def pieces_level(L, args):
+    qual0, off, ln = make_batch(args.reads, args.mean_len)
+    out = {}
+    for share in [float(x) for x in args.share.split(',')]:
+        qual, cut_off, cuts = plant_cuts(qual0, off, ln, share)
+        run = lambda dev: engine.quality_filter_pieces(qual, off, ln, cut_off, cuts, device=dev, **OPTS)  # noqa: E731
+        host = run(-1)
+        res = {'split_reads': int(cut_off[-1]), 'pieces': int(host[2].size), 'piece_bytes': int((host[2]['end'] - host[2]['begin']).sum()),
+               'pieces_cropped': int((host[2]['q']['front'] + host[2]['q']['tail'] > 0).sum()),
+               'pieces_failed': int(((host[2]['q']['flags'] & engine.QUAL_FAIL) != 0).sum())}
+        host_ms, dev_ms, kern, whole = [], [], [], []
+        if args.device >= 0:
+            dev = run(args.device)
+            res['device_equals_host'] = all(a.tobytes() == b.tobytes() for a, b in zip(dev, host))
+        for _ in range(args.repeats):
+            piece_times(L, 0, 1)
+            run(-1)
+            host_ms.append(piece_times(L, 0, 1)[4])
+            if args.device >= 0:
+                run(args.device)
+                dev_ms.append(piece_times(L, 1, 1)[5])
+                run(args.device)                                       # a call of its own with the events on
+                kern.append(piece_times(L, 0, 1)[:4])
+                qual_times(L, 1, 1)
+                engine.quality_filter(qual, off, ln, device=args.device, **OPTS)
+                whole.append(qual_times(L, 0, 1)[:2])
+        res['host_build_ms'] = round(float(np.median(host_ms)), 2)
+        if args.device >= 0:
+            med = [float(np.median([k[j] for k in kern])) for j in range(4)]
+            res.update({'plan_kernels_ms': round(med[0], 3), 'piece_crop_ms': round(med[1], 3), 'piece_sum_ms': round(med[2], 3),
+                        'k_piece_cuts_ms': round(med[3], 3), 'kernel_runs_ms': [[round(x, 3) for x in k] for k in kern],
+                        'device_stage_ms': round(float(np.median(dev_ms)), 2), 'device_stage_runs_ms': [round(x, 2) for x in dev_ms],
+                        'whole_read_crop_ms': round(float(np.median([w[0] for w in whole])), 3),
+                        'whole_read_sum_ms': round(float(np.median([w[1] for w in whole])), 3)})
+        out['share_%g' % share] = res
+    return {'reads': int(ln.size), 'quality_bytes': int(qual0.size), 'repeats': args.repeats, 'opts': OPTS, 'pieces': out}
+
+
 def whole_file(args, tmp):
     from custom_porechop_abi_amd.pipeline import FileTrimmer
     src = os.path.join(tmp, 'in.fastq')
@@ -120,10 +187,12 @@ def main():
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--file-reads', type=int, default=100000)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--pieces', action='store_true')
+    ap.add_argument('--share', default='0.05,1.0')
     args = ap.parse_args()
     L = _lib.lib()
-    res = table_level(L, args)
-    if args.file_reads > 0 and args.device >= 0:
+    res = pieces_level(L, args) if args.pieces else table_level(L, args)
+    if args.file_reads > 0 and args.device >= 0 and not args.pieces:
         tmp = tempfile.mkdtemp(prefix='pcabi_qual_')
         res.update(whole_file(args, tmp))
         os.rmdir(tmp)
